@@ -11,6 +11,10 @@ generator iterations whatever --steps / --warmup are.  Workload at N=1 = BASELIN
 128x128 -> 1024x1024 tiles, filters 128, 16 RRDBs, bf16 storage + bf16 MFMA with fp32 accumulate,
 fp32 master weights / Adam.  Inputs are synthetic N(0,1) tiles resident in HBM in native NHWC layout
 before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps (with the per-launch events its `kernels` / `roofline` come from) and prints
+the line.  `--full` adds the measurements beside the headline: the CPU baseline, 5 more steps without per-launch events and
+the fp8 mode (single GPU).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -296,6 +300,36 @@ def summarise_kernels(prof, elapsed, steps, peak, args, per_layer, with_traffic=
     return roofline, critic_stack, kernels
 
 
+DUMP_SAMPLE = {"generated": 2 << 20, "generator_params": 4 << 20, "critic_params": 4 << 20}     # elements: 40 MB of float32 at most
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, eng, scal):
+    """What a caller of the timed path receives after its last step, as <out_dir>/<name>.npy: every loss scalar of
+    `read_scalars` (float64, shape [1]), the generated batch of that step (its 2 real predictand channels, NHWC) and the fp32
+    master parameters of both networks after their updates (the flat buffers).  An array larger than its DUMP_SAMPLE entry is
+    written as a fixed sample: the elements at DUMP_SEED-seeded random flat indices, in ascending index order -- the same
+    indices for every build, since they depend on the array's size alone.  The default mode's split-K reductions are not
+    bit-reproducible and training amplifies that step by step; with DG_DETERMINISTIC=1 two runs dump identical bits."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in scal.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.array([v], dtype=np.float64))
+    eng.C.P.sync(); eng.G.P.sync()
+
+    def sample(name, t):
+        t = t.reshape(-1)
+        n = DUMP_SAMPLE[name]
+        if t.numel() > n:
+            idx = torch.randint(t.numel(), (n,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+            t = t[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.float().cpu().numpy())
+    sample("generated", eng.G.fake[..., :2])
+    sample("generator_params", eng.G.P.p)
+    sample("critic_params", eng.C.P.p)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -308,10 +342,16 @@ def main():
                          "with uniform-scale operands, everything else as in bf16; "
                          "fp8c = the critic's layers only")
     ap.add_argument("--batch", type=int, default=0, help="override per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline and, on one GPU, the two short extra measurements "
+                         "(5 steps without per-launch events; 5 steps of the fp8 mode)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (losses, generated batch, both networks' parameters) "
+                         "as DIR/<name>.npy; bit-identical from run to run with DG_DETERMINISTIC=1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the two short extra measurements of the default line (5 steps without per-launch events; 5 steps of the fp8 mode)")
+                    help="with --full: skip the two short extra measurements (5 steps without per-launch events; 5 steps of the fp8 mode)")
     ap.add_argument("--per-layer", action="store_true", help="diagnostic: split the `kernels` table by layer geometry (with bytes)")
     ap.add_argument("--graphs", action="store_true", help="replay the iterations as captured HIP graphs (small, launch-bound tiles)")
     ap.add_argument("--check-finite", action="store_true",
@@ -344,7 +384,7 @@ def main():
     if args.batch:
         B = args.batch
     is_f8 = args.dtype in ("fp8", "fp8c")
-    extras = world == 1 and not args.no_extras and not args.graphs and not args.per_layer
+    extras = args.full and world == 1 and not args.no_extras and not args.graphs and not args.per_layer
     nsteps = args.warmup + args.steps + (5 if extras else 0)
     ops, eng, xc, xf, alphas = build_engine(args, args.dtype, world, dist, local, rank, nsteps)
 
@@ -380,8 +420,10 @@ def main():
     roofline, critic_stack, kernels = summarise_kernels(prof, elapsed, args.steps, peak, args, args.per_layer)
     hbm_peak = torch.cuda.max_memory_allocated()
     stacked = bool(eng.stacked)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, scal)
 
-    # ---- extras of the default line (single GPU): the same engine without the per-launch events, then the fp8 mode
+    # ---- extras of --full (single GPU): the same engine without the per-launch events, then the fp8 mode
     bare = fp8 = None
     if extras:
         if not args.no_kernel_timing:
@@ -453,7 +495,7 @@ def main():
             out["without_kernel_events"] = bare
         if fp8 is not None:
             out["fp8"] = fp8
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, (B, S, F_, cin, nrb))
         print(json.dumps(out), flush=True)
     if dist:

@@ -108,9 +108,9 @@ def test_bench_self_launch_rehearsal_line():
 
 
 def test_bench_default_line_carries_fp8_and_event_free_numbers():
-    """The default single-GPU command (small workload here) also reports the fp8 mode (BASELINE configs[4]) and a short region
+    """The single-GPU command with --full (small workload here) also reports the fp8 mode (BASELINE configs[4]) and a short region
     without per-launch events, and is not marked as a rehearsal."""
-    d = _bench("--workload", "mid", "--steps", "5", "--warmup", "1", "--no-cpu-baseline")
+    d = _bench("--workload", "mid", "--steps", "5", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert d["n_gpus"] == 1 and d["rehearsal"] is False and d["dtype"] == "bf16" and d["ranks_seen"][0]["device"] == "cuda:0"
     assert d["roofline"]["frac"] > 0 and d["critic_conv_stack"]["mfma_frac"] > 0
     assert d["without_kernel_events"]["steps"] == 5 and d["without_kernel_events"]["ms_per_step"] > 0
@@ -118,3 +118,24 @@ def test_bench_default_line_carries_fp8_and_event_free_numbers():
     assert f8["steps"] == 5 and f8["value"] > 0 and f8["roofline"]["peak"] == 5000.0 and f8["roofline"]["launches"] > 0
     import math
     assert all(math.isfinite(v) for v in f8["losses"].values())
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """The plain command measures the headline only (no fp8 mode, no event-free region, no CPU baseline); --dump-outputs writes
+    the last timed step's losses, generated batch and parameters as float .npy files, the same files and shapes for the same arguments."""
+    import math
+    import numpy as np
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _bench("--workload", "mid", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "samples/s" and d["dtype"] == "bf16"
+        assert not {"fp8", "without_kernel_events", "cpu_baseline"} & set(d)
+        files = sorted(p.name for p in out.iterdir())
+        assert {"generated.npy", "generator_params.npy", "critic_params.npy", "critic_loss.npy", "g_loss.npy"} <= set(files), files
+        arrs = {f: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and a.size for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert math.isclose(float(arrs["critic_loss.npy"][0]), d["losses"]["critic_loss"], rel_tol=1e-6)
+        runs.append(arrs)
+    assert runs[0].keys() == runs[1].keys() and all(runs[0][f].shape == runs[1][f].shape for f in runs[0])
