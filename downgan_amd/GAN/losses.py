@@ -9,6 +9,12 @@ fallback; raises without the native library or a GPU).
                                                         win 7, data_range 1)   -> csrc/metrics.hip via msssim.MsSsim
   wass_loss(real, fake, device)       losses.py:8-9     real - fake
   divergence_loss / vorticity_loss    losses.py:119-193 std-normalised MSE of finite-difference fields -> dg_div_vort_sums
+  eof_loss(X, hr, fake, device)       losses.py:72-116  std-normalised MSE of the (uncentred) projections on EOFs X [K, C, P]
+                                                        -> dg_eof_project; returns a Python float like the reference
+  low_pass_eof_batch(Z, pcas, fine, transformer, device, fake=False)
+                                      losses.py:196-228 sum_k Z[b, c, k] pcas[k, c] for c = 0, 1 (no mean added back); with
+                                                        fake, Z = the transformers' centred projections of `fine`
+                                                        -> dg_eof_project, dg_eof_reconstruct
 
 Unlike the reference's SSIM_Loss this one does NOT normalise its arguments in place (the reference's mutation is a side
 effect that nothing downstream reads: the metrics pass is the last use of the batch, wasserstein.py:138-146).
@@ -98,6 +104,71 @@ def vorticity_loss(hr, fake, device=None):
     """losses.py:158-193."""
     m, n = _div_vort(hr, fake, device)
     return _scalar(_o(device), _std_normalised_mse(m[5:], n))
+
+
+def _eof_project(o, y, E, K, ld_k, ld_c, m=None):
+    """Z [B, C, K] fp32 = (y - m) . E over the pixels of the NCHW batch y (one launch pair, csrc/eof.hip)."""
+    y = y.detach().to(o.device, torch.float32).contiguous()
+    Z = torch.empty(y.shape[0], y.shape[1], K, dtype=torch.float32, device=o.device)
+    o.eof_project(o.eof_fields(y), m, E, K, ld_k, ld_c, Z)
+    return Z
+
+
+def eof_loss(X, hr, fake, device=None):
+    """losses.py:72-116.  X [K, C, P]: hr, fake [B, C, H, W] are projected (uncentred) on X[k, c]; each of the two projection sets
+    [B, K, C] is divided by its own unbiased std over all its values; the MSE of the two is returned as a float (``.item()``)."""
+    o = _o(device)
+    K, Cx, P = X.shape
+    B, Cn, H, W = hr.shape
+    assert Cx == Cn and P == H * W and tuple(fake.shape) == tuple(hr.shape), (tuple(X.shape), tuple(hr.shape), tuple(fake.shape))
+    E = torch.as_tensor(X).detach().to(o.device, torch.float32).contiguous()
+    zr = _eof_project(o, hr, E, K, Cn * P, P).double().cpu()
+    zf = _eof_project(o, fake, E, K, Cn * P, P).double().cpu()
+    return float(((zf / zf.std() - zr / zr.std()) ** 2).mean())
+
+
+_staged_pca = {}
+
+
+def _pca_arrays(o, t):
+    """(mean_ [P], components_ [K, P]) of a transformer as fp32 device tensors: a native channel view's own, or a foreign object's
+    (a fitted sklearn PCA, say) staged once and cached."""
+    if torch.is_tensor(t.components_) and t.components_.device == o.device and t.components_.dtype == torch.float32 \
+            and t.components_.is_contiguous() and t.mean_.is_contiguous():
+        return t.mean_, t.components_
+    key = (id(t), id(t.mean_), id(t.components_), str(o.device))
+    if key not in _staged_pca:
+        m = torch.as_tensor(t.mean_).to(o.device, torch.float32).contiguous()
+        e = torch.as_tensor(t.components_).to(o.device, torch.float32).contiguous()
+        _staged_pca[key] = (t, m, e)
+    return _staged_pca[key][1], _staged_pca[key][2]
+
+
+def low_pass_eof_batch(Z, pcas, fine, transformer, device=None, fake=False):
+    """losses.py:196-228.  pcas [K, C, P], Z [B, C, K] (channels 0 and 1 used) -> lows [B, 2, H, W] with
+    lows[b, c] = sum_k Z[b, c, k] pcas[k, c] (no mean added back).  With ``fake`` Z is recomputed from ``fine`` through
+    ``transformer[0]`` / ``transformer[1]`` (centred projections, like sklearn's ``transform``)."""
+    o = _o(device)
+    B, H, W = fine.size(0), fine.size(2), fine.size(3)
+    P = H * W
+    E = torch.as_tensor(pcas).detach().to(o.device, torch.float32).contiguous()
+    K, Cp = E.shape[0], E.shape[1]
+    assert E.shape[2] == P and Cp >= 2, (tuple(E.shape), P)
+    if fake:
+        y = fine.detach().to(o.device, torch.float32).contiguous()
+        parts = []
+        for c in range(2):
+            m, comps = _pca_arrays(o, transformer[c])
+            Zc = torch.empty(B, 1, comps.shape[0], dtype=torch.float32, device=o.device)
+            o.eof_project(o.eof_fields(y[:, c:c + 1]), m, comps, comps.shape[0], P, 0, Zc)
+            parts.append(Zc)
+        Z = torch.cat(parts, dim=1)
+    else:
+        Z = torch.as_tensor(Z)[:, :2].to(o.device, torch.float32).contiguous()
+    assert Z.shape[2] == K, (tuple(Z.shape), K)
+    lows = torch.empty(B, 2, H, W, dtype=torch.float32, device=o.device)
+    o.eof_reconstruct(Z, E, Cp * P, P, P, None, lows)
+    return lows
 
 
 metrics_to_calculate = {"MAE": content_loss, "MSE": content_MSELoss, "MSSSIM": SSIM_Loss, "Wass": wass_loss}   # hyperparams.py:38-43

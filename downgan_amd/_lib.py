@@ -76,6 +76,14 @@ class FiniteBufs(C.Structure):
     _fields_ = [("ptr", C.c_void_p * FINITE_MAX), ("n", C.c_int64 * FINITE_MAX), ("dtype", C.c_int * FINITE_MAX), ("nbuf", C.c_int)]
 
 
+EOF_MAX_C, EOF_MAX_K = 8, 64
+
+
+class EofFields(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("dtype", C.c_int), ("T", C.c_int), ("C", C.c_int), ("P", C.c_int),
+                ("ld_t", C.c_int64), ("ld_c", C.c_int64), ("ld_p", C.c_int64)]
+
+
 MINMAX_PARTS = 256
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _PROTOS = {
@@ -137,6 +145,12 @@ _PROTOS = {
     "dg_set_deterministic_workspace": [_vp, _i64],
     "dg_deterministic": [],
     "dg_count_nonfinite": [C.POINTER(FiniteBufs), _vp, _vp],
+    "dg_eof_mean": [C.POINTER(EofFields), _vp, _vp],
+    "dg_eof_gram": [C.POINTER(EofFields), _vp, _i, _vp, _vp, _vp],
+    "dg_eof_components": [C.POINTER(EofFields), _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp],
+    "dg_eof_flip": [_vp, _i, _i, _i, _i64, _i64, _vp, _vp],
+    "dg_eof_project": [C.POINTER(EofFields), _vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp],
+    "dg_eof_reconstruct": [_vp, _i, _i, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp],
 }
 EXPORTS = ["dg_version"] + list(_PROTOS)
 

@@ -757,6 +757,87 @@ class HipOps:
         check(self.lib.dg_div_vort_sums(self.dg, _ptr(hr), pix_layout(hr)[0], _ptr(fake), pix_layout(fake)[0], N, H, W, _ptr(sums),
                                         self._stream()), "dg_div_vort_sums")
 
+    # ------------------------------------------------------------------ EOF analysis (csrc/eof.hip)
+    @staticmethod
+    def eof_fields(t, nhwc=False):
+        """dg_eof_fields of a series of fields: ``[T, C, H, W]`` / ``[T, C, P]`` with a unit-stride pixel plane (NCHW), or with
+        ``nhwc`` a dense-pixel ``[n, H, W, c]`` store (the resident feed).  fp32 or bf16, on this device; the caller keeps ``t`` alive."""
+        dt = {torch.float32: _lib.DG_F32, torch.bfloat16: _lib.DG_BF16}.get(t.dtype)
+        assert dt is not None and t.is_cuda, (t.dtype, t.device)
+        if nhwc:
+            n, H, W, c = t.shape
+            assert t.stride(3) == 1 and t.stride(2) == c and t.stride(1) == W * c, (t.shape, t.stride())
+            T, Cn, P, ld_t, ld_c, ld_p = n, c, H * W, t.stride(0), 1, c
+        else:
+            if t.dim() == 4:
+                assert t.stride(3) == 1 and t.stride(2) == t.shape[3], (t.shape, t.stride())
+                t = t.flatten(2)
+            assert t.dim() == 3 and t.stride(2) == 1, (t.shape, t.stride())
+            T, Cn, P, ld_t, ld_c, ld_p = t.shape[0], t.shape[1], t.shape[2], t.stride(0), t.stride(1), 1
+        assert 1 <= Cn <= _lib.EOF_MAX_C and P < 2 ** 31 and T < 2 ** 31, (T, Cn, P)
+        return _lib.EofFields(base=t.data_ptr(), dtype=dt, T=T, C=Cn, P=P, ld_t=ld_t, ld_c=ld_c, ld_p=ld_p)
+
+    def _eof_workspace(self, floats):
+        ws = getattr(self, "_eof_ws", None)
+        if ws is None or ws.numel() < floats:
+            self._eof_ws = ws = torch.empty(int(floats), dtype=torch.float32, device=self.device)
+        return ws
+
+    EOF_GRAM_SLICE = 32768        # most pixels one fp32 partial slab of the Gram sums (as 512-pixel chains) before the fp64 slice sum;
+    EOF_GRAM_SLICE_WIDE = 2048    # ... with more than 4 channels (one-level chains in the kernel)
+    EOF_WS_CAP = 4 << 30          # bytes of Gram partial slabs at most (fewer, longer slices above it)
+
+    def eof_gram_slices(self, T, C, P):
+        """Number of P slices of a Gram: slabs of at most EOF_GRAM_SLICE pixels, at least ~2048 workgroups, under EOF_WS_CAP."""
+        nb = (T + 63) // 64
+        ntiles = nb * (nb + 1) // 2
+        ns = max(-(-P // (self.EOF_GRAM_SLICE if C <= 4 else self.EOF_GRAM_SLICE_WIDE)), -(-2048 // ntiles))
+        ns = min(ns, max(1, self.EOF_WS_CAP // (ntiles * C * 16384)))
+        return max(1, min(ns, -(-P // 64))), ntiles
+
+    def eof_mean(self, f, mu):
+        """mu [C, P] fp32 = mean over the T fields of the descriptor ``f`` (eof_fields)."""
+        assert mu.dtype == torch.float32 and mu.is_contiguous() and mu.numel() == f.C * f.P
+        check(self.lib.dg_eof_mean(C.byref(f), _ptr(mu), self._stream()), "dg_eof_mean")
+
+    def eof_gram(self, f, mu, G):
+        """G [C, T, T] fp64 = centred Gram of every channel (split-P f32 MFMA, fixed-order fp64 slice sum)."""
+        assert G.dtype == torch.float64 and G.is_contiguous() and G.numel() == f.C * f.T * f.T
+        ns, ntiles = self.eof_gram_slices(f.T, f.C, f.P)
+        ws = self._eof_workspace(ns * ntiles * f.C * 4096)
+        check(self.lib.dg_eof_gram(C.byref(f), _ptr(mu), ns, _ptr(ws), _ptr(G), self._stream()), "dg_eof_gram")
+
+    def eof_components(self, f, mu, A, K, E, amax):
+        """E [C, K, P] fp32 (contiguous) = A^T-weighted sums of the centred fields; A [C, T, roundup16(K)] fp32; amax [C, K] int64
+        zeroed here, then flipped: sklearn's sign rule applied in place."""
+        Cn, P = f.C, f.P
+        assert A.dtype == torch.float32 and A.is_contiguous() and tuple(A.shape) == (Cn, f.T, (K + 15) // 16 * 16)
+        assert E.dtype == torch.float32 and E.is_contiguous() and tuple(E.shape) == (Cn, K, P)
+        assert amax.dtype == torch.int64 and amax.numel() == Cn * K
+        amax.zero_()
+        st = self._stream()
+        check(self.lib.dg_eof_components(C.byref(f), _ptr(mu), _ptr(A), K, _ptr(E), P, K * P, _ptr(amax), st), "dg_eof_components")
+        check(self.lib.dg_eof_flip(_ptr(E), Cn, K, P, P, K * P, _ptr(amax), st), "dg_eof_flip")
+
+    def eof_project(self, f, m, E, K, ld_k, ld_c, Z):
+        """Z [B, C, K] fp32 = (y - m) . E over the pixels (m None: uncentred); E fp32 with unit pixel stride, rows at ld_k, channels
+        at ld_c (elements)."""
+        assert Z.dtype == torch.float32 and Z.is_contiguous() and tuple(Z.shape) == (f.T, f.C, K)
+        assert E.dtype == torch.float32 and E.is_cuda
+        nta = (f.T + 63) // 64
+        ns = max(1, min(-(-1024 // nta), -(-f.P // 64)))
+        ws = self._eof_workspace(ns * nta * f.C * 4096)
+        check(self.lib.dg_eof_project(C.byref(f), _ptr(m), _ptr(E), K, ld_k, ld_c, ns, _ptr(ws), _ptr(Z), self._stream()),
+              "dg_eof_project")
+
+    def eof_reconstruct(self, Z, E, ld_k, ld_c, P, mu, out):
+        """out [B, C, P] fp32 = Z . E (+ mu [C, P] when given); Z [B, C, K] fp32 contiguous."""
+        B, Cn, K = Z.shape
+        assert Z.dtype == torch.float32 and Z.is_contiguous() and E.dtype == torch.float32
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * Cn * P
+        check(self.lib.dg_eof_reconstruct(_ptr(Z), B, Cn, K, _ptr(E), ld_k, ld_c, P, _ptr(mu), _ptr(out), self._stream()),
+              "dg_eof_reconstruct")
+
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32
         check(self.lib.dg_sum_strided(_ptr(inp), n, stride, float(scale), _ptr(out), self._stream()), "dg_sum_strided")

@@ -452,6 +452,49 @@ int dg_set_deterministic_workspace(void* ws, int64_t bytes);
 int dg_deterministic(void);      /* 1 while a workspace is registered */
 int dg_count_nonfinite(const dg_finite_bufs* bufs, uint32_t* counts, void* stream);
 
+/* ---- EOF analysis (csrc/eof.hip) -------------------------------------------------------------------------------------
+ * Empirical orthogonal functions = one PCA per channel of a time series of fields: the reference fits sklearn `PCA` on the host
+ * (DoWnGAN/helpers/prep_gan.py:226-255) and projects / reconstructs with torch in `eof_loss` (DoWnGAN/GAN/losses.py:72-116)
+ * and `low_pass_eof_batch` (losses.py:196-228).  Here the fit is mean -> centred Gram (f32 MFMA) -> host eigh of the T x T
+ * Gram -> components, and projection / reconstruction stream the fields once.
+ * Fields are read through one strided descriptor: element (t, c, p), p = h*W + w, sits at base + t*ld_t + c*ld_c + p*ld_p
+ * (ELEMENTS of `dtype`, DG_F32 or DG_BF16; bf16 is widened on load).  NCHW tensors: ld_p = 1, ld_c = H*W; the resident feed's
+ * [n, H, W, c] store: ld_p = c, ld_c = 1.  C <= DG_EOF_MAX_C.  Components E are fp32 with unit pixel stride: E[c][k][p] at
+ * E + k*ld_k + c*ld_c + p ([C, K, P]: ld_k = P, ld_c = K*P; the reference's [K, C, P]: ld_k = C*P, ld_c = P).
+ * All reductions are deterministic: fixed-order sums, no float atomics; two calls on the same data are bit-identical.
+ *
+ * dg_eof_mean: mu[c][p] = mean over t (fp64 accumulation).
+ * dg_eof_gram: G[c][i][j] = sum_p (x[i,c,p] - mu[c,p]) (x[j,c,p] - mu[c,p]) as fp64 [C][T][T].  Centring is fused into the
+ *   operand load; upper-triangle 64 x 64 tiles only, mirrored.  The P range is split into `nslice` slices: ws holds
+ *   nslice * ntiles * C * 4096 fp32 partial slabs, ntiles = nb (nb + 1) / 2, nb = ceil(T / 64); slices are summed in order in
+ *   fp64.  1 <= nslice <= ceil(P / 64).
+ * dg_eof_components: E[c][k][p] = sum_t A[c][t][k] (x[t,c,p] - mu[c,p]) for k < K, A fp32 [C][T][lda] (lda = K rounded up to a
+ *   multiple of 16, zero beyond K).  amax[c][k] (pre-zeroed) receives the position of the entry of largest magnitude of row
+ *   (c, k), ties to the lowest p, as the key (|E| bits << 32) | (0xffffffff - p) (integer max: order-independent).
+ * dg_eof_flip: negates every row (c, k) of E whose entry at the amax position is negative (sklearn's sign rule:
+ *   svd_flip(u_based_decision=False) makes the entry of largest magnitude of every component positive).
+ * dg_eof_project: Z[b][c][k] = sum_p (y[b,c,p] - m[c,p]) E[c][k][p] (fp32 [B][C][K], B = y->T; m NULL = uncentred).  A
+ *   split-P product on the Gram kernel's machinery: ws holds nslice * ceil(B/64) * ceil(K/64) * C * 4096 fp32.
+ * dg_eof_reconstruct: out[b][c][p] = sum_k Z[b][c][k] E[c][k][p] (+ mu[c][p] when mu is not NULL), fp32 NCHW [B][C][P]; Z is
+ *   fp32 [B][C][K]. */
+#define DG_EOF_MAX_C 8
+#define DG_EOF_MAX_K 64
+typedef struct dg_eof_fields {
+  const void* base;
+  int dtype;
+  int T, C, P;
+  int64_t ld_t, ld_c, ld_p;
+} dg_eof_fields;
+int dg_eof_mean(const dg_eof_fields* x, float* mu, void* stream);
+int dg_eof_gram(const dg_eof_fields* x, const float* mu, int nslice, float* ws, double* G, void* stream);
+int dg_eof_components(const dg_eof_fields* x, const float* mu, const float* A, int K, float* E, int64_t ld_k, int64_t ld_c,
+                      unsigned long long* amax, void* stream);
+int dg_eof_flip(float* E, int C, int K, int P, int64_t ld_k, int64_t ld_c, const unsigned long long* amax, void* stream);
+int dg_eof_project(const dg_eof_fields* y, const float* m, const float* E, int K, int64_t ld_k, int64_t ld_c, int nslice,
+                   float* ws, float* Z, void* stream);
+int dg_eof_reconstruct(const float* Z, int B, int C, int K, const float* E, int64_t ld_k, int64_t ld_c, int P, const float* mu,
+                       float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
