@@ -146,9 +146,10 @@ class WassersteinGAN:
         o.gp_finish(e.ss, B, B * e.world, e.hp.gp_lambda, 0.0, e.coef, e._sc("gp_ret"))
         return float(e._sc("gp_ret").item())
 
-    def gen_batch_and_log_metrics(self, coarse, fine):
+    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
-        returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales)."""
+        returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
+        pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass)."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -160,15 +161,18 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n)
+            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf)
+        return e.metrics_pass(xc, xf, spectra=spectra)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
     # set at the epoch's end, per-epoch means (post_epoch_metric_mean), and the per-epoch checkpoint of both networks
     log_metrics = True
+    # opt-in: radially averaged power spectra of the real and generated fields of the metrics passes (train batches, test
+    # loader), accumulated on the device and reported per epoch in summary["spectra"]; rides on the metrics pass's G forward
+    log_spectra = False
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -176,19 +180,47 @@ class WassersteinGAN:
         keys = [k for k in ("MAE", "MSE", "MSSSIM", "Wass") if rows and rows[0].get(k) is not None]
         return {k: sum(r[k] for r in rows) / len(rows) for k in keys}
 
+    def _spectra_pair(self, fine):
+        from ..spectra import RadialSpectrum
+        N, dev = fine.shape[-1], self._engine.ops.device if self._engine is not None else self.G.device
+        return RadialSpectrum(self.G.n_predictands, N, device=dev), RadialSpectrum(self.G.n_predictands, N, device=dev)
+
+    def _test_pair(self, spectra, data):
+        """The test loader's accumulator pair when spectra are logged, else None."""
+        if not self.log_spectra:
+            return None
+        if "test" not in spectra:
+            spectra["test"] = self._spectra_pair(data[1])
+        return spectra["test"]
+
+    def _spectra_summary(self, pair):
+        """{"real", "fake": [C][K] mean spectra, "lsd": [C] log-spectral distance of fake to real, "fields": count} of an
+        accumulator pair, summed over the data-parallel ranks first."""
+        from ..spectra import log_spectral_distance
+        real, fake = (acc.reduce_(self.dist).mean() for acc in pair)
+        return {"real": real.cpu().tolist(), "fake": fake.cpu().tolist(),
+                "lsd": [float(v) for v in log_spectral_distance(real, fake)], "fields": pair[0].count}
+
     def _train_epoch(self, dataloader, testdataloader=None, epoch=0):
         """wasserstein.py:120-179: every batch = critic iteration, generator iteration when num_steps % critic_iterations == 0
         (same batch), metrics pass (:140-146); then the epoch means of the train metrics, the metrics over the test loader
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
         log, train_metrics, test_metrics = [], [], []
+        spectra = {}                                                              # "train" / "test" -> (real, fake)
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
             out = dict(self._critic_train_iteration(coarse, fine, _keep_g=gen_step))
             if gen_step:
                 out.update(self._generator_train_iteration(coarse, fine, _reuse_g=True))
-            if self.log_metrics:
+            if self.log_spectra:
+                if "train" not in spectra:
+                    spectra["train"] = self._spectra_pair(fine)
+                m = self.gen_batch_and_log_metrics(coarse, fine, spectra=spectra["train"])
+                if self.log_metrics:
+                    train_metrics.append(m)
+            elif self.log_metrics:
                 train_metrics.append(self.gen_batch_and_log_metrics(coarse, fine))   # :140-146
             self.num_steps += 1
             if self._engine is not None:
@@ -201,11 +233,16 @@ class WassersteinGAN:
                 # :157-168.  EVERY test batch is evaluated, whatever its size (the engine re-binds, state carried over); the
                 # reference's epoch mean is the mean over batches (post_epoch_metric_mean), a ragged batch counting as one
                 for data in testdataloader:
-                    test_metrics.append(self.gen_batch_and_log_metrics(data[0], data[1]))
+                    test_metrics.append(self.gen_batch_and_log_metrics(data[0], data[1], spectra=self._test_pair(spectra, data)))
                 if not test_metrics:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
+        if self.log_spectra:
+            if testdataloader is not None and not self.log_metrics:
+                for data in testdataloader:
+                    self.gen_batch_and_log_metrics(data[0], data[1], spectra=self._test_pair(spectra, data))
+            summary["spectra"] = {k: self._spectra_summary(v) for k, v in spectra.items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

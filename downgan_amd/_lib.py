@@ -77,6 +77,7 @@ class FiniteBufs(C.Structure):
 
 
 EOF_MAX_C, EOF_MAX_K = 8, 64
+RAPSD_MAX_N = 2048
 
 
 class EofFields(C.Structure):
@@ -151,7 +152,11 @@ _PROTOS = {
     "dg_eof_flip": [_vp, _i, _i, _i, _i64, _i64, _vp, _vp],
     "dg_eof_project": [C.POINTER(EofFields), _vp, _vp, _i, _i64, _i64, _i, _vp, _vp, _vp],
     "dg_eof_reconstruct": [_vp, _i, _i, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp],
+    "dg_rapsd_ws_bytes": [_i, _i, _i],
+    "dg_rapsd": [C.POINTER(EofFields), _i, _vp, _vp, _vp, _vp],
+    "dg_rapsd_ring_counts": [_i, C.POINTER(_i64)],
 }
+_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None
@@ -212,7 +217,7 @@ def lib():
         l.dg_version.argtypes = []
         for name, args in _PROTOS.items():
             fn = getattr(l, name)
-            fn.restype = C.c_int
+            fn.restype = _RESTYPES.get(name, C.c_int)
             fn.argtypes = args
         _lib = l
     return _lib

@@ -1,0 +1,319 @@
+// Radially averaged power spectra (include/downgan_hip.h "Radially averaged power spectra") of square N x N fields,
+// N a power of two in [16, DG_RAPSD_MAX_N], read through the EOF field descriptor (NCHW, [n, H, W, c], padded NHWC; fp32 / bf16).
+//   rapsd_twiddle_kernel   tw[m] = exp(-2 pi i m / N), from double sincospi, rounded to fp32 once
+//   rapsd_count_kernel     ring pixel counts (the same integer ring test as the host's dg_rapsd_ring_counts)
+//   rapsd_row_kernel       two real rows packed as one complex N-point FFT (Stockham radix-4, radix-2 last stage when log2 N
+//                          is odd, in LDS), split into the two half spectra u = 0..N/2, written transposed: spec[f][u][h]
+//   rapsd_col_kernel       per line u of a field: complex N-point FFT along h, |X|^2 / N^2 with the Hermitian weight (1 for
+//                          u = 0 and u = N/2, 2 otherwise), ring sums per workgroup (a slice of the lines) in fp64
+//   rapsd_field_kernel     slices summed in a fixed order (fp64), divided by the ring counts -> per-field spectra
+//   rapsd_sum_kernel       sum[c][k] = sum over t of the per-field spectra, in t order
+// Ring k holds the frequencies (u, v) (signed, |u|, |v| <= N/2) with (2k-1)^2 <= 4 (u^2 + v^2) < (2k+1)^2, evaluated in integers:
+// r^2 in [k^2 - k + 1, k^2 + k] (k = 0: r^2 = 0).  Rings k > N/2 (the corners) are dropped.  No float atomics anywhere: two
+// calls on the same data are bit-identical.
+#include "dg_internal.h"
+
+namespace {
+
+constexpr int RAPSD_PTS = 2048;                                     // complex points per workgroup and LDS buffer
+constexpr int RAPSD_KQ = (DG_RAPSD_MAX_N / 2 + 1 + 255) / 256;      // rings per thread in the column pass
+
+__host__ __device__ inline int isqrt_floor(int x) {
+  int s = (int)sqrtf((float)x);
+  while (s * s > x) --s;
+  while ((s + 1) * (s + 1) <= x) ++s;
+  return s;
+}
+
+// |v| range of ring k on line u: v^2 in [lo, hi] with r^2 = u^2 + v^2 in ring k.  Empty when vmin > vmax.
+__host__ __device__ inline void ring_span(int u, int k, int N, int& vmin, int& vmax) {
+  const int hi = k * k + k - u * u;
+  if (hi < 0) { vmin = 1; vmax = 0; return; }
+  int lo = (k == 0 ? 0 : k * k - k + 1) - u * u;
+  lo = lo < 0 ? 0 : lo;
+  vmax = isqrt_floor(hi);
+  vmax = vmax > N / 2 ? N / 2 : vmax;
+  vmin = isqrt_floor(lo);
+  if (vmin * vmin < lo) ++vmin;
+}
+
+__host__ __device__ inline long long ring_count(int k, int N) {
+  long long n = 0;
+  for (int u = 0; u <= N / 2; ++u) {
+    int vmin, vmax;
+    ring_span(u, k, N, vmin, vmax);
+    if (vmin > vmax) continue;
+    long long nv = 2LL * (vmax - vmin + 1) - (vmin == 0) - (vmax == N / 2);   // v = 0 and v = -N/2 exist once
+    n += (u == 0 || u == N / 2 ? 1 : 2) * nv;
+  }
+  return n;
+}
+
+__device__ __forceinline__ float2 cmul(float2 a, float2 b) {
+  return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
+}
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+
+// RAPSD_PTS / N forward complex FFTs of length N at once, Stockham autosort between buf[0] (input) and buf[1]; returns the
+// buffer that holds the result (natural order).  Stage with span p and radix R: task i of an FFT (T = N / R tasks) reads
+// x[i + j T], twiddles them by W^(j k N / (R p)) with k = i mod p, and writes the R-point DFT to y[(i - k) R + k + r p].
+__device__ int fft_lds(float2 (*buf)[RAPSD_PTS], const float2* tw, int N, int logN) {
+  const int nfft = RAPSD_PTS >> logN;
+  int src = 0;
+  for (int p = 1, logp = 0; p < N;) {
+    const int R = (p * 4 <= N) ? 4 : 2, logR = R == 4 ? 2 : 1;
+    const int logT = logN - logR, T = 1 << logT;
+    const int tws = N >> (logp + logR);
+    const float2* x = buf[src];
+    float2* y = buf[src ^ 1];
+    for (int task = threadIdx.x; task < nfft * T; task += 256) {
+      const int j = task >> logT, i = task & (T - 1);
+      const float2* xj = x + (j << logN);
+      float2* yj = y + (j << logN);
+      const int k = i & (p - 1), o = ((i - k) << logR) + k;
+      if (R == 4) {
+        const float2 u0 = xj[i];
+        const float2 u1 = cmul(xj[i + T], tw[k * tws]);
+        const float2 u2 = cmul(xj[i + 2 * T], tw[2 * k * tws]);
+        const float2 u3 = cmul(xj[i + 3 * T], tw[3 * k * tws]);
+        const float2 v0 = cadd(u0, u2), v1 = csub(u0, u2), v2 = cadd(u1, u3), d = csub(u1, u3);
+        const float2 v3 = make_float2(d.y, -d.x);                   // -i (u1 - u3)
+        yj[o] = cadd(v0, v2);
+        yj[o + p] = cadd(v1, v3);
+        yj[o + 2 * p] = csub(v0, v2);
+        yj[o + 3 * p] = csub(v1, v3);
+      } else {
+        const float2 u0 = xj[i], u1 = cmul(xj[i + T], tw[k * tws]);
+        yj[o] = cadd(u0, u1);
+        yj[o + p] = csub(u0, u1);
+      }
+    }
+    __syncthreads();
+    src ^= 1;
+    p <<= logR;
+    logp += logR;
+  }
+  return src;
+}
+
+__global__ void rapsd_twiddle_kernel(float2* tw, int N) {
+  const int m = blockIdx.x * 256 + threadIdx.x;
+  if (m >= N) return;
+  double s, c;
+  sincospi(2.0 * m / N, &s, &c);
+  tw[m] = make_float2((float)c, (float)-s);
+}
+
+__global__ void rapsd_count_kernel(double* cnt, int N) {
+  const int k = blockIdx.x * 256 + threadIdx.x;
+  if (k <= N / 2) cnt[k] = (double)ring_count(k, N);
+}
+
+struct RapsdRow {
+  const void* base;
+  long long ld_t, ld_c, ld_p;
+  int C, N, logN;
+  long long npairs;           // T * C * N / 2 row pairs
+  const float2* tw;
+  float2* spec;               // [F][N/2 + 1][N]
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void rapsd_row_kernel(RapsdRow a) {
+  __shared__ float2 buf[2][RAPSD_PTS];
+  __shared__ float2 tw[DG_RAPSD_MAX_N];
+  const int N = a.N, logN = a.logN, nfft = RAPSD_PTS >> logN, K = N / 2 + 1, half = N / 2;
+  const long long g0 = (long long)blockIdx.x * nfft;
+  for (int m = threadIdx.x; m < N; m += 256) tw[m] = a.tw[m];
+  const T* base = reinterpret_cast<const T*>(a.base);
+  for (int idx = threadIdx.x; idx < RAPSD_PTS; idx += 256) {
+    const int j = idx >> logN, w = idx & (N - 1);
+    const long long g = g0 + j;
+    float2 z = make_float2(0.f, 0.f);
+    if (g < a.npairs) {
+      const long long f = g / half;
+      const int h = 2 * (int)(g % half);
+      const T* q = base + (f / a.C) * a.ld_t + (f % a.C) * a.ld_c + ((long long)h * N + w) * a.ld_p;
+      z = make_float2(ld_elem(q), ld_elem(q + (long long)N * a.ld_p));
+    }
+    buf[0][idx] = z;
+  }
+  __syncthreads();
+  const float2* Z = buf[fft_lds(buf, tw, N, logN)];
+  // Z = A + i B for the rows (h, h + 1): A[u] = (Z[u] + conj Z[-u]) / 2, B[u] = -i (Z[u] - conj Z[-u]) / 2.  The pair index
+  // runs fastest, so consecutive lanes store the adjacent rows h of one line u: spec[f][u][h .. h + 1] is one 16-byte store.
+  for (int idx = threadIdx.x; idx < K * nfft; idx += 256) {
+    const int u = idx >> (11 - logN), j = idx & (nfft - 1);
+    const long long g = g0 + j;
+    if (g >= a.npairs) continue;
+    const float2 zu = Z[(j << logN) + u], zm = Z[(j << logN) + ((N - u) & (N - 1))];
+    const float2 s = make_float2(0.5f * (zu.x + zm.x), 0.5f * (zu.y - zm.y));     // (Z[u] + conj Z[-u]) / 2
+    const float2 d = make_float2(0.5f * (zu.x - zm.x), 0.5f * (zu.y + zm.y));     // (Z[u] - conj Z[-u]) / 2
+    const long long f = g / half;
+    const int h = 2 * (int)(g % half);
+    *reinterpret_cast<float4*>(a.spec + (f * K + u) * N + h) = make_float4(s.x, s.y, d.y, -d.x);
+  }
+}
+
+struct RapsdCol {
+  const float2* spec;
+  const float2* tw;
+  int N, logN, S, L;          // S slices of L lines (a multiple of the FFTs per workgroup) per field
+  double* part;               // [F][S][N/2 + 1]
+};
+
+__global__ __launch_bounds__(256) void rapsd_col_kernel(RapsdCol a) {
+  __shared__ float2 buf[2][RAPSD_PTS];
+  __shared__ float2 tw[DG_RAPSD_MAX_N];
+  const int N = a.N, logN = a.logN, nfft = RAPSD_PTS >> logN, K = N / 2 + 1;
+  const long long f = blockIdx.x / a.S;
+  const int s = blockIdx.x % a.S;
+  const int u_end = min(K, (s + 1) * a.L);
+  const float inv = 1.f / ((float)N * (float)N);              // a power of two: exact
+  for (int m = threadIdx.x; m < N; m += 256) tw[m] = a.tw[m];
+  double acc[RAPSD_KQ];
+#pragma unroll
+  for (int q = 0; q < RAPSD_KQ; ++q) acc[q] = 0.0;
+  for (int u0 = s * a.L; u0 < u_end; u0 += nfft) {
+    const int nl = min(nfft, u_end - u0);
+    const float4* src4 = reinterpret_cast<const float4*>(a.spec + (f * K + u0) * N);   // nl whole lines, contiguous
+    for (int idx = threadIdx.x; idx < RAPSD_PTS / 2; idx += 256) {
+      const float4 v = (2 * idx >> logN) < nl ? src4[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+      buf[0][2 * idx] = make_float2(v.x, v.y);
+      buf[0][2 * idx + 1] = make_float2(v.z, v.w);
+    }
+    __syncthreads();
+    const int r = fft_lds(buf, tw, N, logN);
+    float* pw = reinterpret_cast<float*>(buf[r ^ 1]);
+    for (int idx = threadIdx.x; idx < RAPSD_PTS; idx += 256) {
+      const int u = u0 + (idx >> logN);
+      const float2 X = buf[r][idx];
+      pw[idx] = fmaf(X.x, X.x, X.y * X.y) * inv * (u == 0 || u == N / 2 ? 1.f : 2.f);
+    }
+    __syncthreads();
+    for (int j = 0; j < nl; ++j) {
+      const float* pl = pw + (j << logN);
+#pragma unroll
+      for (int q = 0; q < RAPSD_KQ; ++q) {
+        const int k = threadIdx.x + 256 * q;
+        if (k >= K) continue;
+        int vmin, vmax;
+        ring_span(u0 + j, k, N, vmin, vmax);
+        double sum = 0.0;
+        for (int v = vmin; v <= vmax; ++v) {
+          sum += (double)pl[v];
+          if (v != 0 && v != N / 2) sum += (double)pl[N - v];
+        }
+        acc[q] += sum;
+      }
+    }
+    __syncthreads();                                            // the next batch overwrites buf
+  }
+  double* out = a.part + (f * a.S + s) * K;
+#pragma unroll
+  for (int q = 0; q < RAPSD_KQ; ++q) {
+    const int k = threadIdx.x + 256 * q;
+    if (k < K) out[k] = acc[q];
+  }
+}
+
+// one thread per (field, ring): the slices in order
+__global__ __launch_bounds__(256) void rapsd_field_kernel(const double* part, const double* cnt, long long F, int S, int K,
+                                                          double* pf, double* per_field) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= F * K) return;
+  const long long f = idx / K;
+  const int k = (int)(idx % K);
+  const double* q = part + f * S * K + k;
+  double s = 0.0;
+  for (int i = 0; i < S; ++i) s += q[(long long)i * K];
+  s /= cnt[k];
+  pf[idx] = s;
+  if (per_field) per_field[idx] = s;
+}
+
+// one thread per (channel, ring): the fields in t order
+__global__ __launch_bounds__(256) void rapsd_sum_kernel(const double* pf, int Tn, int C, int K, double* sum) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= C * K) return;
+  double s = 0.0;
+  for (int t = 0; t < Tn; ++t) s += pf[(long long)t * C * K + idx];
+  sum[idx] = s;
+}
+
+// workspace: twiddles, counts, spec, slice partials, per-field spectra (each 256-byte aligned)
+struct RapsdWs {
+  size_t tw, cnt, spec, part, pf, bytes;
+  int S, L;
+};
+
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+bool rapsd_n_ok(int N) { return N >= 16 && N <= DG_RAPSD_MAX_N && (N & (N - 1)) == 0; }
+
+RapsdWs rapsd_ws(long long F, int N) {
+  RapsdWs w;
+  const int K = N / 2 + 1, nfft = RAPSD_PTS / N;
+  const int nb = (K + nfft - 1) / nfft;                         // line batches per field
+  long long S = (2048 + F - 1) / F;                             // ~2048 column workgroups
+  S = S < 1 ? 1 : S > nb ? nb : S;
+  w.S = (int)S;
+  w.L = (nb + w.S - 1) / w.S * nfft;
+  w.tw = 0;
+  w.cnt = w.tw + align256((size_t)N * 8);
+  w.spec = w.cnt + align256((size_t)K * 8);
+  w.part = w.spec + align256((size_t)F * K * N * 8);
+  w.pf = w.part + align256((size_t)F * w.S * K * 8);
+  w.bytes = w.pf + align256((size_t)F * K * 8);
+  return w;
+}
+
+}  // namespace
+
+extern "C" size_t dg_rapsd_ws_bytes(int T, int C, int N) {
+  if (T < 1 || C < 1 || C > DG_EOF_MAX_C || !rapsd_n_ok(N)) return 0;
+  return rapsd_ws((long long)T * C, N).bytes;
+}
+
+extern "C" int dg_rapsd_ring_counts(int N, int64_t* counts) {
+  if (!rapsd_n_ok(N) || !counts) return DG_ERR_BAD_SHAPE;
+  for (int k = 0; k <= N / 2; ++k) counts[k] = ring_count(k, N);
+  return DG_OK;
+}
+
+extern "C" int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_field, double* sum, void* stream) {
+  if (!x || !x->base || !ws || !rapsd_n_ok(N) || x->T < 1 || x->C < 1 || x->C > DG_EOF_MAX_C || x->P != N * N || x->ld_t < 0 ||
+      x->ld_c < 0 || x->ld_p < 0)
+    return DG_ERR_BAD_SHAPE;
+  if (x->dtype != DG_F32 && x->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
+  const long long F = (long long)x->T * x->C;
+  const int K = N / 2 + 1, logN = __builtin_ctz(N), nfft = RAPSD_PTS / N;
+  const RapsdWs w = rapsd_ws(F, N);
+  const long long npairs = F * (N / 2);
+  const long long row_blocks = (npairs + nfft - 1) / nfft, col_blocks = F * w.S;
+  if (row_blocks > 0x7fffffffLL || col_blocks > 0x7fffffffLL || F * K > 0x7fffffffLL * 256LL) return DG_ERR_BAD_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* b = reinterpret_cast<char*>(ws);
+  float2* tw = reinterpret_cast<float2*>(b + w.tw);
+  double* cnt = reinterpret_cast<double*>(b + w.cnt);
+  float2* spec = reinterpret_cast<float2*>(b + w.spec);
+  double* part = reinterpret_cast<double*>(b + w.part);
+  double* pf = reinterpret_cast<double*>(b + w.pf);
+  hipLaunchKernelGGL(rapsd_twiddle_kernel, dim3((N + 255) / 256), dim3(256), 0, st, tw, N);
+  hipLaunchKernelGGL(rapsd_count_kernel, dim3((K + 255) / 256), dim3(256), 0, st, cnt, N);
+  RapsdRow r;
+  r.base = x->base; r.ld_t = x->ld_t; r.ld_c = x->ld_c; r.ld_p = x->ld_p;
+  r.C = x->C; r.N = N; r.logN = logN; r.npairs = npairs; r.tw = tw; r.spec = spec;
+  if (x->dtype == DG_F32) hipLaunchKernelGGL(rapsd_row_kernel<float>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
+  else hipLaunchKernelGGL(rapsd_row_kernel<bf16_t>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
+  RapsdCol c;
+  c.spec = spec; c.tw = tw; c.N = N; c.logN = logN; c.S = w.S; c.L = w.L; c.part = part;
+  hipLaunchKernelGGL(rapsd_col_kernel, dim3((unsigned)col_blocks), dim3(256), 0, st, c);
+  hipLaunchKernelGGL(rapsd_field_kernel, dim3((unsigned)((F * K + 255) / 256)), dim3(256), 0, st, (const double*)part,
+                     (const double*)cnt, F, w.S, K, pf, per_field);
+  if (sum)
+    hipLaunchKernelGGL(rapsd_sum_kernel, dim3((unsigned)((x->C * K + 255) / 256)), dim3(256), 0, st, (const double*)pf, x->T, x->C,
+                       K, sum);
+  return dg_check_launch();
+}

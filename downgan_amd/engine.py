@@ -1215,14 +1215,16 @@ class TrainEngine:
         if apply_update:
             self._allreduce_and_step(G.P, defer=True)             # :83 (overlaps with the next critic iteration's real pass)
 
-    def metrics_pass(self, coarse, fine, n_valid=None):
+    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
         MSSSIM is None when the tile is too small for 5 scales (pytorch_msssim asserts side > 96).
         ``n_valid`` < B: only the first n_valid samples of the (padded) batch count -- a smaller test batch evaluated on the
         training engine's buffers instead of re-binding the whole engine to its size; every sample is independent on this path
-        (no batch norm), so the padded rows change nothing in the first n_valid."""
+        (no batch norm), so the padded rows change nothing in the first n_valid.
+        ``spectra``: a ``(real, fake)`` pair of ``spectra.RadialSpectrum`` that receive the spectra of ``fine[:n]`` and of the
+        ``fake[:n]`` this pass generates anyway (no extra generator forward); the returned metrics are the same."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1231,6 +1233,9 @@ class TrainEngine:
         m.zero_()
         o.l1(fine[:n], fake[:n], m[0:1])
         o.sqdiff(fine[:n], fake[:n], m[1:2])
+        if spectra is not None:
+            spectra[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
+            spectra[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

@@ -759,15 +759,17 @@ class HipOps:
 
     # ------------------------------------------------------------------ EOF analysis (csrc/eof.hip)
     @staticmethod
-    def eof_fields(t, nhwc=False):
+    def eof_fields(t, nhwc=False, channels=None):
         """dg_eof_fields of a series of fields: ``[T, C, H, W]`` / ``[T, C, P]`` with a unit-stride pixel plane (NCHW), or with
-        ``nhwc`` a dense-pixel ``[n, H, W, c]`` store (the resident feed).  fp32 or bf16, on this device; the caller keeps ``t`` alive."""
+        ``nhwc`` a dense-pixel ``[n, H, W, c]`` store (the resident feed); ``channels`` (nhwc only): read just the leading channels
+        of a padded store (the generator's output).  fp32 or bf16, on this device; the caller keeps ``t`` alive."""
         dt = {torch.float32: _lib.DG_F32, torch.bfloat16: _lib.DG_BF16}.get(t.dtype)
         assert dt is not None and t.is_cuda, (t.dtype, t.device)
         if nhwc:
             n, H, W, c = t.shape
             assert t.stride(3) == 1 and t.stride(2) == c and t.stride(1) == W * c, (t.shape, t.stride())
-            T, Cn, P, ld_t, ld_c, ld_p = n, c, H * W, t.stride(0), 1, c
+            assert channels is None or 1 <= channels <= c, (channels, c)
+            T, Cn, P, ld_t, ld_c, ld_p = n, c if channels is None else channels, H * W, t.stride(0), 1, c
         else:
             if t.dim() == 4:
                 assert t.stride(3) == 1 and t.stride(2) == t.shape[3], (t.shape, t.stride())
@@ -837,6 +839,26 @@ class HipOps:
         assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == B * Cn * P
         check(self.lib.dg_eof_reconstruct(_ptr(Z), B, Cn, K, _ptr(E), ld_k, ld_c, P, _ptr(mu), _ptr(out), self._stream()),
               "dg_eof_reconstruct")
+
+    # ------------------------------------------------------------------ radially averaged power spectra (csrc/spectra.hip)
+    def rapsd_ws_bytes(self, T, Cn, N):
+        """Workspace bytes of one dg_rapsd call over T fields of Cn channels, N x N (0: not a valid shape)."""
+        return int(self.lib.dg_rapsd_ws_bytes(int(T), int(Cn), int(N)))
+
+    def rapsd(self, f, N, per_field=None, sum=None):
+        """Ring-averaged power spectra of the N x N fields of the descriptor ``f`` (eof_fields, P = N*N): per_field [T, C, N/2+1]
+        and / or sum [C, N/2+1] (sum over the T fields, in order), fp64 contiguous, either may be None.  The workspace is cached
+        on this object and grows to the largest call."""
+        K = N // 2 + 1
+        for out, n in ((per_field, f.T * f.C * K), (sum, f.C * K)):
+            assert out is None or (out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n and out.is_cuda)
+        nb = self.rapsd_ws_bytes(f.T, f.C, N)
+        assert nb > 0, (f.T, f.C, N)
+        ws = getattr(self, "_rapsd_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._rapsd_ws = ws = None
+            self._rapsd_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_rapsd(C.byref(f), int(N), _ptr(ws), _ptr(per_field), _ptr(sum), self._stream()), "dg_rapsd")
 
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32

@@ -24,6 +24,7 @@
 #ifndef DOWNGAN_HIP_H
 #define DOWNGAN_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -494,6 +495,29 @@ int dg_eof_project(const dg_eof_fields* y, const float* m, const float* E, int K
                    float* ws, float* Z, void* stream);
 int dg_eof_reconstruct(const float* Z, int B, int C, int K, const float* E, int64_t ld_k, int64_t ld_c, int P, const float* mu,
                        float* out, void* stream);
+
+/* ---- Radially averaged power spectra (csrc/spectra.hip) ----------------------------------------------------------------
+ * The standard per-scale diagnostic of a downscaling generator: the radially averaged power spectral density (RAPSD) of real
+ * and generated fields.  Fields are square, N x N with N a power of two, 16 <= N <= DG_RAPSD_MAX_N, read through the EOF
+ * descriptor with P = N*N, p = h*N + w (NCHW fp32, the resident feed's [n, H, W, c] store, or the generator's padded NHWC
+ * output: ld_p = padded channel count, C = real channels; bf16 is widened on load).  For one field x:
+ *   P[u][v] = |FFT2(x)[u][v]|^2 / N^2, with signed integer frequencies u, v in [-N/2, N/2);
+ *   ring k holds (u, v) with (2k-1)^2 <= 4 (u^2 + v^2) < (2k+1)^2, evaluated exactly in integers; K = N/2 + 1 rings, pixels
+ *   of rings k > N/2 (the corners) are dropped; no windowing, no mean removal (ring 0 holds the mean's power);
+ *   S[k] = mean of P over ring k.
+ * Row pass: two real rows as one complex N-point FFT (Stockham radix-4 in LDS, fp32 twiddles rounded once from double), half
+ * spectra written transposed; column pass: N-point FFT per line u, power with the Hermitian weight, ring sums per workgroup;
+ * the partials are summed in a fixed order in fp64.  No float atomics: two calls on the same data are bit-identical.
+ *
+ * dg_rapsd_ws_bytes: workspace bytes of dg_rapsd for T fields of C channels (0 for an invalid shape); ~8 (N/2 + 1) N bytes per
+ *   field (the half spectra) plus small fp64 partials.
+ * dg_rapsd: per_field[t][c][k] (fp64 [T][C][N/2+1], may be NULL) and sum[c][k] = sum over t of per_field[t][c][k] in t order
+ *   (fp64 [C][N/2+1], may be NULL).  x->P must equal N*N, x->C <= DG_EOF_MAX_C.
+ * dg_rapsd_ring_counts: host-side, counts[k] = number of frequencies (u, v) in ring k, k = 0..N/2 (the divisors the kernels use). */
+#define DG_RAPSD_MAX_N 2048
+size_t dg_rapsd_ws_bytes(int T, int C, int N);
+int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_field, double* sum, void* stream);
+int dg_rapsd_ring_counts(int N, int64_t* counts);
 
 #ifdef __cplusplus
 }
