@@ -146,10 +146,12 @@ class WassersteinGAN:
         o.gp_finish(e.ss, B, B * e.world, e.hp.gp_lambda, 0.0, e.coef, e._sc("gp_ret"))
         return float(e._sc("gp_ret").item())
 
-    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None):
+    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
-        pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass)."""
+        pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
+        ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
+        mode, real as staged and generated as written)."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -161,10 +163,10 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra)
+            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf, spectra=spectra)
+        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -173,6 +175,13 @@ class WassersteinGAN:
     # opt-in: radially averaged power spectra of the real and generated fields of the metrics passes (train batches, test
     # loader), accumulated on the device and reported per epoch in summary["spectra"]; rides on the metrics pass's G forward
     log_spectra = False
+    # opt-in: value histograms of the same real and generated fields (quantiles, W1 / KS distances, tail exceedances), reported
+    # per epoch in summary["distributions"]; distribution_spec None = histograms.HistSpec.zscore(n_predictands)
+    log_distributions = False
+    distribution_spec = None
+    distribution_q = (0.001, 0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 0.999)
+    distribution_exceed_q = (0.99, 0.999, 0.9999)
+    distribution_results = None  # the last epoch's {"train" / "test": (real, fake) histograms.Histogram} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -185,13 +194,42 @@ class WassersteinGAN:
         N, dev = fine.shape[-1], self._engine.ops.device if self._engine is not None else self.G.device
         return RadialSpectrum(self.G.n_predictands, N, device=dev), RadialSpectrum(self.G.n_predictands, N, device=dev)
 
-    def _test_pair(self, spectra, data):
-        """The test loader's accumulator pair when spectra are logged, else None."""
-        if not self.log_spectra:
-            return None
-        if "test" not in spectra:
-            spectra["test"] = self._spectra_pair(data[1])
-        return spectra["test"]
+    def _dist_pair(self):
+        from ..histograms import HistSpec, ValueHistogram
+        spec = self.distribution_spec if self.distribution_spec is not None else HistSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return ValueHistogram(spec, device=dev), ValueHistogram(spec, device=dev)
+
+    def _hooks(self, acc, part, fine):
+        """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}}), created on first use; {} when none is on."""
+        kw = {}
+        if self.log_spectra:
+            sp = acc.setdefault("spectra", {})
+            if part not in sp:
+                sp[part] = self._spectra_pair(fine)
+            kw["spectra"] = sp[part]
+        if self.log_distributions:
+            d = acc.setdefault("distributions", {})
+            if part not in d:
+                d[part] = self._dist_pair()
+            kw["distributions"] = d[part]
+        return kw
+
+    def _distribution_summary(self, part, pair):
+        """The JSON-serialisable summary of an accumulator pair (summed over the data-parallel ranks first): channel names,
+        field count, quantiles / moments / extrema / out-of-range and NaN counts of the real and the generated values, and per
+        channel their W1 and KS distances and the generated values' exceedance of the real tail quantiles."""
+        from ..histograms import exceedance, ks_distance, wasserstein1
+        real, fake = (acc.reduce_(self.dist).result() for acc in pair)
+        q, eq = list(self.distribution_q), list(self.distribution_exceed_q)
+        side = lambda h: {"quantiles": h.quantile(q).tolist(), "mean": h.mean().tolist(), "std": h.std().tolist(),
+                          "min": h.min().tolist(), "max": h.max().tolist(), "out_of_range": h.out_of_range().tolist(),
+                          "nan": h.nan().tolist()}
+        self.distribution_results[part] = (real, fake)
+        return {"channels": list(real.spec.names), "fields": real.fields, "q": q, "exceed_q": eq, "real": side(real),
+                "fake": side(fake), "w1": wasserstein1(real, fake).tolist(), "ks": ks_distance(real, fake).tolist(),
+                "exceed_fake": exceedance(real, fake, eq).tolist()}
 
     def _spectra_summary(self, pair):
         """{"real", "fake": [C][K] mean spectra, "lsd": [C] log-spectral distance of fake to real, "fields": count} of an
@@ -207,17 +245,16 @@ class WassersteinGAN:
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
         log, train_metrics, test_metrics = [], [], []
-        spectra = {}                                                              # "train" / "test" -> (real, fake)
+        acc = {}                                              # "spectra" / "distributions" -> {"train" / "test": (real, fake)}
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
             out = dict(self._critic_train_iteration(coarse, fine, _keep_g=gen_step))
             if gen_step:
                 out.update(self._generator_train_iteration(coarse, fine, _reuse_g=True))
-            if self.log_spectra:
-                if "train" not in spectra:
-                    spectra["train"] = self._spectra_pair(fine)
-                m = self.gen_batch_and_log_metrics(coarse, fine, spectra=spectra["train"])
+            hooks = self._hooks(acc, "train", fine)
+            if hooks:
+                m = self.gen_batch_and_log_metrics(coarse, fine, **hooks)
                 if self.log_metrics:
                     train_metrics.append(m)
             elif self.log_metrics:
@@ -233,16 +270,20 @@ class WassersteinGAN:
                 # :157-168.  EVERY test batch is evaluated, whatever its size (the engine re-binds, state carried over); the
                 # reference's epoch mean is the mean over batches (post_epoch_metric_mean), a ragged batch counting as one
                 for data in testdataloader:
-                    test_metrics.append(self.gen_batch_and_log_metrics(data[0], data[1], spectra=self._test_pair(spectra, data)))
+                    test_metrics.append(self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1])))
                 if not test_metrics:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
-        if self.log_spectra:
+        if self.log_spectra or self.log_distributions:
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
-                    self.gen_batch_and_log_metrics(data[0], data[1], spectra=self._test_pair(spectra, data))
-            summary["spectra"] = {k: self._spectra_summary(v) for k, v in spectra.items()}
+                    self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
+            if self.log_spectra:
+                summary["spectra"] = {k: self._spectra_summary(v) for k, v in acc.get("spectra", {}).items()}
+            if self.log_distributions:
+                self.distribution_results = {}
+                summary["distributions"] = {k: self._distribution_summary(k, v) for k, v in acc.get("distributions", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

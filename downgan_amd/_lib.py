@@ -78,11 +78,17 @@ class FiniteBufs(C.Structure):
 
 EOF_MAX_C, EOF_MAX_K = 8, 64
 RAPSD_MAX_N = 2048
+HIST_MAX_BINS, HIST_MAX_OUT = 4096, EOF_MAX_C + 1
 
 
 class EofFields(C.Structure):
     _fields_ = [("base", C.c_void_p), ("dtype", C.c_int), ("T", C.c_int), ("C", C.c_int), ("P", C.c_int),
                 ("ld_t", C.c_int64), ("ld_c", C.c_int64), ("ld_p", C.c_int64)]
+
+
+class HistSpec(C.Structure):
+    _fields_ = [("nbins", C.c_int), ("speed_u", C.c_int), ("speed_v", C.c_int), ("lo", C.c_float * HIST_MAX_OUT),
+                ("inv_w", C.c_float * HIST_MAX_OUT), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C)]
 
 
 MINMAX_PARTS = 256
@@ -155,8 +161,11 @@ _PROTOS = {
     "dg_rapsd_ws_bytes": [_i, _i, _i],
     "dg_rapsd": [C.POINTER(EofFields), _i, _vp, _vp, _vp, _vp],
     "dg_rapsd_ring_counts": [_i, C.POINTER(_i64)],
+    "dg_hist_ws_bytes": [C.POINTER(EofFields), C.POINTER(HistSpec)],
+    "dg_hist": [C.POINTER(EofFields), C.POINTER(HistSpec), _vp, _vp, _vp, _vp, _vp],
+    "dg_hist_host_bins": [C.POINTER(HistSpec), _vp, _i, _i64, _vp],
 }
-_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

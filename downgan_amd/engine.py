@@ -1215,7 +1215,7 @@ class TrainEngine:
         if apply_update:
             self._allreduce_and_step(G.P, defer=True)             # :83 (overlaps with the next critic iteration's real pass)
 
-    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None):
+    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1224,7 +1224,10 @@ class TrainEngine:
         training engine's buffers instead of re-binding the whole engine to its size; every sample is independent on this path
         (no batch norm), so the padded rows change nothing in the first n_valid.
         ``spectra``: a ``(real, fake)`` pair of ``spectra.RadialSpectrum`` that receive the spectra of ``fine[:n]`` and of the
-        ``fake[:n]`` this pass generates anyway (no extra generator forward); the returned metrics are the same."""
+        ``fake[:n]`` this pass generates anyway (no extra generator forward); the returned metrics are the same.
+        ``distributions``: likewise a ``(real, fake)`` pair of ``histograms.ValueHistogram``.  Both read the fields as stored:
+        in bf16 mode the staged real fields and the generated ones are bf16 (spacing 0.031 on [4, 8), coarser than the default
+        bin width of 0.0098), so the histograms are those of the bf16 values."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1236,6 +1239,9 @@ class TrainEngine:
         if spectra is not None:
             spectra[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
             spectra[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if distributions is not None:
+            distributions[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
+            distributions[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

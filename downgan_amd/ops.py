@@ -860,6 +860,28 @@ class HipOps:
             self._rapsd_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
         check(self.lib.dg_rapsd(C.byref(f), int(N), _ptr(ws), _ptr(per_field), _ptr(sum), self._stream()), "dg_rapsd")
 
+    # ------------------------------------------------------------------ value histograms (csrc/histogram.hip)
+    def hist_ws_bytes(self, f, spec):
+        """Workspace bytes of one dg_hist call over the descriptor ``f`` with the _lib.HistSpec ``spec`` (0: invalid)."""
+        return int(self.lib.dg_hist_ws_bytes(C.byref(f), C.byref(spec)))
+
+    def hist(self, f, spec, counts, moments, extrema):
+        """Accumulate the histograms of the fields of ``f`` (eof_fields) under ``spec`` (_lib.HistSpec): counts int64
+        [nout, nbins + 3] +=, moments fp64 [nout, 2] (sum, sum of squares) +=, extrema fp32 [nout, 2] (min, max) min / max.
+        The workspace is cached on this object."""
+        nout = f.C + (1 if spec.speed_u >= 0 else 0)
+        for out, dt, n in ((counts, torch.int64, nout * (spec.nbins + 3)), (moments, torch.float64, 2 * nout),
+                           (extrema, torch.float32, 2 * nout)):
+            assert out.dtype == dt and out.is_contiguous() and out.numel() == n and out.is_cuda, (out.dtype, out.shape, n)
+        nb = self.hist_ws_bytes(f, spec)
+        assert nb > 0, (f.T, f.C, f.P, spec.nbins)
+        ws = getattr(self, "_hist_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._hist_ws = ws = None
+            self._hist_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_hist(C.byref(f), C.byref(spec), _ptr(ws), _ptr(counts), _ptr(moments), _ptr(extrema), self._stream()),
+              "dg_hist")
+
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32
         check(self.lib.dg_sum_strided(_ptr(inp), n, stride, float(scale), _ptr(out), self._stream()), "dg_sum_strided")

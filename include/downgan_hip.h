@@ -519,6 +519,37 @@ size_t dg_rapsd_ws_bytes(int T, int C, int N);
 int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_field, double* sum, void* stream);
 int dg_rapsd_ring_counts(int N, int64_t* counts);
 
+/* ---- Value histograms (csrc/histogram.hip) ------------------------------------------------------------------------------
+ * The distribution check of a downscaling generator: per-channel histograms of real and generated fields, read in place
+ * through the EOF descriptor (any T, P; NCHW fp32 / bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC
+ * output: ld_p = padded channel count, C = real channels).  Every operation below is one correctly rounded fp32 operation,
+ * never contracted:
+ *   y_c = (x_c * scale[c]) + offset[c]                     input channel c (scale 1, offset 0: y = x, -0 read as +0)
+ *   s   = sqrt(y_u * y_u + y_v * y_v)                       speed_u >= 0: appended as output channel C (nout = C + 1)
+ *   t   = (y - lo[j]) * inv_w[j]                            output channel j; inv_w = fp32(nbins / (hi - lo)) rounded once
+ *   bin = NaN -> nbins + 2;  t < 0 (-inf too) -> 0;  t >= nbins (+inf too) -> nbins + 1;  else 1 + (int)t
+ * Subnormals are kept.  counts: int64 [nout][nbins + 3] (underflow, nbins interior bins, overflow, NaN), exact for any T * P;
+ * moments: fp64 [nout][2] (sum, sum of squares of the finite y); extrema: fp32 [nout][2] (min, max of the finite y).  dg_hist
+ * ACCUMULATES: counts and moments +=, extrema min / max (the caller initialises them).  Each workgroup keeps its histogram in
+ * LDS (ds_add_u32) and adds the non-zero bins to counts with 64-bit integer atomics; moments and extrema go through per-
+ * workgroup partials summed in workgroup order.  No float atomics: two calls on the same data are bit-identical.
+ *
+ * dg_hist_ws_bytes: workspace bytes of dg_hist for these fields (0 for an invalid descriptor or spec).
+ * dg_hist_host_bins: host-side, the same transform and bin rule for x fp32 [C][n] (planar): bins int32 [nout][n]. */
+#define DG_HIST_MAX_BINS 4096
+#define DG_HIST_MAX_OUT (DG_EOF_MAX_C + 1)
+typedef struct dg_hist_spec {
+  int nbins;                       /* 1 .. DG_HIST_MAX_BINS, every output channel */
+  int speed_u, speed_v;            /* input channels of the speed channel, or -1, -1: none */
+  float lo[DG_HIST_MAX_OUT];       /* per output channel, finite */
+  float inv_w[DG_HIST_MAX_OUT];    /* per output channel, finite and > 0 */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel */
+} dg_hist_spec;
+size_t dg_hist_ws_bytes(const dg_eof_fields* x, const dg_hist_spec* s);
+int dg_hist(const dg_eof_fields* x, const dg_hist_spec* s, void* ws, int64_t* counts, double* moments, float* extrema,
+            void* stream);
+int dg_hist_host_bins(const dg_hist_spec* s, const float* x, int C, int64_t n, int32_t* bins);
+
 #ifdef __cplusplus
 }
 #endif
