@@ -40,6 +40,7 @@ class WassersteinGAN:
         self.last = {}
         self.metrics_log = []
 
+    engine_class = TrainEngine   # the native engine _build creates (WassersteinGANFS: TrainEngineFS)
     check_finite = False         # debug: NaN / Inf census after every iteration (TrainEngine(check_finite=True); the reference
                                  # runs with torch.autograd.set_detect_anomaly(True), wasserstein.py:13)
 
@@ -80,8 +81,8 @@ class WassersteinGAN:
 
     def _build(self, B, cin, S, carry):
         ops = backend.make_ops(self.G.dtype, self.G.device)
-        e = TrainEngine(ops, S, self.G.filters, cin, B, hp.as_engine_hp(B), self.G.n_predictands,
-                        self.G.num_res_blocks, self.G.num_upsample, dist=self.dist, check_finite=self.check_finite)
+        e = self.engine_class(ops, S, self.G.filters, cin, B, hp.as_engine_hp(B), self.G.n_predictands,
+                              self.G.num_res_blocks, self.G.num_upsample, dist=self.dist, check_finite=self.check_finite)
         if carry is not None:
             e.G.P.import_state(carry[0]); e.C.P.import_state(carry[1])
         return e, carry is not None

@@ -65,6 +65,7 @@ class ParamStore:
         self.size = 0
         self.conv_dgrad = {}   # name -> (cout_p, cin_p)
         self.after_refresh = []   # callbacks run whenever the compute-precision packs were re-derived (fp8 weight forms)
+        self._pending = None      # a parked parameter update (see ``defer``): set by defer, cleared by sync
 
     def add(self, name, shape):
         n = int(math.prod(shape))
@@ -85,8 +86,6 @@ class ParamStore:
     # A parameter update whose gradient all-reduce is still in flight on RCCL's stream can be parked here; every accessor
     # below completes it first, so whatever needs the parameters (or the gradient buffer) next waits for it, and anything
     # that does not (the generator's forward after a critic update) overlaps with the collective.
-    _pending = None
-
     def defer(self, fn):
         self.sync()
         self._pending = fn
@@ -220,7 +219,7 @@ class NativeCritic:
         # Needs 64-channel wave tiles, i.e. every conv width >= 128 (cfg2: yes; the 16-filter configs keep plain masks).
         use_bits = os.environ.get("DG_NO_MASK_BITS") is None and all(c >= 128 and c % 64 == 0 for c in self.c_pad[1:])
         self.f8 = bool(getattr(o, "f8", False))
-        # STACKED passes (critic_iteration_stacked): the real, the generated and the interpolated batch of a critic iteration go
+        # STACKED passes (TrainEngine._critic_passes_stacked): the real, the generated and the interpolated batch of a critic iteration go
         # through the layers as ONE batch of 3B -- a third of the launches, each three times as long (the conv kernels gain 4-9 %
         # forward, 1-3 % backward from the longer grids) -- so every per-sample buffer holds 3B samples; the single-pass methods
         # below work on the first B.  Needs the bit masks (the tangent pass reads a row range of them), the fused FC1 gradient and,
@@ -243,10 +242,10 @@ class NativeCritic:
         self._outpre_all = o.zeros(cap, FC_OUT_P, dtype=torch.float32)
         self._out_all = o.zeros(cap, FC_OUT_P, dtype=torch.float32)
         self._dout_all = o.zeros(cap, FC_OUT_P, dtype=torch.float32)
-        self.h1pre, self.h1, self.outpre = self._h1pre_all[:batch], self._h1_all[:batch], self._outpre_all[:batch]
-        self.out, self.dout = self._out_all[:batch], self._dout_all[:batch]
         self.uh1 = o.zeros(batch, FC_HID_LD, dtype=torch.float32)
-        self._tan = None
+        self._cv_cache = {}               # N -> self.convs re-bound to a batch of N (_cvn)
+        # the tangent pass's own buffers: created by the first gp_tangent, kept
+        self._tan = self._th1pre = self._th1 = self._ones = None
         # FC1's weight gradient (1.9 GB fp32 at cfg2) is formed ONCE per critic iteration from the rows of all three passes
         # (dg_linear_dw_wide) instead of being read-modify-written by each: slots 0-2 of these buffers hold FC1's input rows
         # (real activation, fake activation, penalty tangent) and the matching adjoint rows; slot 3 = passes without one.
@@ -291,7 +290,7 @@ class NativeCritic:
         # the adjoints of the loss passes (d out = +-1 / B) and of the penalty pass (d out = 1) differ by the batch size: one exponent
         # set per kind of pass over the same byte buffers ("loss": usu[l][1], "gp": us_exp_gp[l])
         self.us_exp_gp = [o.zeros(self.us[l].shape[-1] // 32, dtype=torch.uint8) if self.wg8[l] else None for l in range(8)]
-        self._us_gp_exp_ok = False
+        self._us_gp_exp_ok = False        # us_exp_gp[l] initialised: set by _update_exponents("gp"), never cleared
         self.tan_exp = [o.zeros(self.acts[l].shape[-1] // 32, dtype=torch.uint8) if l + 1 < 8 and self.wg8[l + 1] else None for l in range(8)]
         self._tanu = None
         self.skip_dead = os.environ.get("DG_F8_KEEP_BF16") is None      # do not store bf16 tensors that only fp8 readers follow (dg_epilogue.skip_y)
@@ -304,8 +303,14 @@ class NativeCritic:
         nb0 = self.acts[0].shape[-1] // 32
         self._a0_amax = o.zeros(nb0, dtype=torch.int32) if self.l0u else None
         self._t0_amax = o.zeros(nb0, dtype=torch.int32) if self.l0u else None
-        self._act_exp_ok = self._us_exp_ok = self._tan_exp_ok = False     # exponents of the role initialised by an earlier pass
-        self._u_act_live = False                                          # this pass's forward wrote valid uniform-scale activations
+        # fp8 pass state.  "Exponents of the role initialised by an earlier pass" (never cleared once set):
+        self._act_exp_ok = self._us_exp_ok = False    # actu[l][1] / usu[l][1]: set by _update_exponents("loss")
+        self._tan_exp_ok = False                      # tan_exp[l]: set at the end of the first gp_tangent
+        # What the LAST pass of its kind left behind (every forward / backward sets or clears them):
+        self._u_act_live = False                      # forward: wrote valid uniform-scale activations actu (for_wgrad, exponents exist)
+        self._us_live = False                         # backward: wrote valid uniform-scale adjoints usu
+        self._act_stored = [True] * 8                 # forward: bf16 acts[l] was stored (False: skipped, no bf16 reader may follow)
+        self._us_stored = [True] * 8                  # backward: bf16 us[l] was stored (likewise)
 
     def _requantise_weights(self):
         o, P = self.ops, self.P
@@ -375,24 +380,36 @@ class NativeCritic:
                 f8kw["xq"] = self.actu[0]             # (bytes, block exponents): the exponents are the scale row of every pixel
             elif self.l0u and l == 0:                 # bootstrap pass: MXFP8 copy as before, and the census starts
                 f8kw["out_amax"] = self._a0_amax
-            # the bf16 activation itself is dead when the next conv reads the MXFP8 copy, the masks are bits and the only other
-            # reader -- layer l + 1's weight gradient -- is the fp8 kernel (or does not run in this pass): not stored then
-            if self.f8 and self.skip_dead and l <= 6 and self.actq[l] is not None and self.act_bits is not None \
-                    and (o.f8_eligible(cv, "fwd") or (l == 0 and self._l0_f8_out)) \
-                    and (not for_wgrad or (want_u and self.wg8[l + 1] and self._us_exp_ok)) and not (l0u and l == 0):
+            if not (l0u and l == 0) and self._activation_unread(l, for_wgrad):
                 f8kw["skip_y"] = True
+            self._act_stored[l] = not f8kw.get("skip_y", False)
             o.conv_fwd(cv, cur, P.w(f"features.{2 * l}.weight"), self.acts[l],
                        bias=P.master("features.0.bias") if l == 0 else None, act=C_SLOPE,
                        out_bits=self.act_bits[l] if self.act_bits else None, **f8kw)
             cur = self.acts[l]
-        y7 = self.acts[7].view(self.B, self.fc_k)
-        self.h1pre.zero_()
-        o.linear_fwd(y7, P.w2d("classifier.0.weight"), self.h1pre, o_real=FC_HID, net="C")
-        o.bias_act(self.h1pre, P.master("classifier.0.bias"), self.h1, act=C_SLOPE)
-        self.outpre.zero_()
-        o.linear_fwd(self.h1, P.w2d("classifier.2.weight"), self.outpre, o_real=1, net="C")
-        o.bias_act(self.outpre, P.master("classifier.2.bias"), self.out)
-        return self.out
+        return self._head_forward(self.acts[7].view(self.B, self.fc_k), 1)
+
+    def _activation_unread(self, l, for_wgrad):
+        """Forward: the bf16 activation of layer l itself is dead when the next conv reads the MXFP8 copy, the masks are bits and
+        the only other reader -- layer l + 1's weight gradient -- is the fp8 kernel (or does not run in this pass): not stored then."""
+        return bool(self.f8 and self.skip_dead and l <= 6 and self.actq[l] is not None and self.act_bits is not None
+                    and (self.ops.f8_eligible(self.convs[l], "fwd") or (l == 0 and self._l0_f8_out))
+                    and (not for_wgrad or (self._u_act_live and self.wg8[l + 1] and self._us_exp_ok)))
+
+    def _head_forward(self, y7, n):
+        """critic.py:96-100 on ``n`` passes of B rows each (1, or 3 stacked): FC1 -> bias / LeakyReLU -> FC2 -> bias.  Returns out (fp32)."""
+        o, P, B = self.ops, self.P, self.B
+        h1pre, h1, outpre, out = (t[:n * B] for t in (self._h1pre_all, self._h1_all, self._outpre_all, self._out_all))
+        passes = [slice(p * B, (p + 1) * B) for p in range(n)]
+        h1pre.zero_()
+        for rows in passes:                               # the split-K FC1 kernel takes up to 32 rows per call
+            o.linear_fwd(y7[rows], P.w2d("classifier.0.weight"), h1pre[rows], o_real=FC_HID, net="C")
+        o.bias_act(h1pre, P.master("classifier.0.bias"), h1, act=C_SLOPE)
+        outpre.zero_()
+        for rows in passes:
+            o.linear_fwd(h1[rows], P.w2d("classifier.2.weight"), outpre[rows], o_real=1, net="C")
+        o.bias_act(outpre, P.master("classifier.2.bias"), out)
+        return out
 
     # ---- adjoint chain (backward of a forward just run on x) ---------------------------------------
     def backward(self, x, dout_value, wgrad=True, dx=None, fc1_slot=None, u_role="loss"):
@@ -402,21 +419,10 @@ class NativeCritic:
         to ``fc1_flush`` (the forward must have used the same slot)."""
         o, P = self.ops, self.P
         uh1 = self.uh1 if fc1_slot is None else self._uh1_all[fc1_slot * self.B:(fc1_slot + 1) * self.B]
-        self.dout.zero_()
-        o.fill_col(self.dout, 0, dout_value)
-        y7 = self.acts[7].view(self.B, self.fc_k)
-        if wgrad:
-            o.linear_dw(self.dout, self.h1, P.grad("classifier.2.weight"), o_real=1, net="C")
-            o.colsum(self.dout, P.grad("classifier.2.bias"))
-        o.linear_dx(self.dout, P.w2d("classifier.2.weight"), uh1, mask=self.h1, mask_slope=C_SLOPE, o_real=1, net="C")
-        if wgrad:
-            if fc1_slot is None:
-                o.linear_dw(uh1[:, :FC_HID_P], y7, P.grad("classifier.0.weight"), o_real=FC_HID, net="C")
-            o.colsum(uh1, P.grad("classifier.0.bias"))
-        o.linear_dx(uh1[:, :FC_HID_P], P.w2d("classifier.0.weight"), self.us[7].view(self.B, self.fc_k),
-                    mask=y7, mask_slope=C_SLOPE, o_real=FC_HID, net="C")
+        self._head_backward(self.acts[7].view(self.B, self.fc_k), self.us[7].view(self.B, self.fc_k), (dout_value,),
+                            1 if wgrad else 0, uh1, fc1_slot is not None)
         # fp8 weight gradients: which exponent set this pass's adjoint copies are written with (None: nobody reads them)
-        us_u = self.f8 and ((u_role == "loss" and wgrad and self._us_exp_ok) or (u_role == "gp" and self._us_gp_exp_ok))
+        us_u = self._us_live = self.f8 and ((u_role == "loss" and wgrad and self._us_exp_ok) or (u_role == "gp" and self._us_gp_exp_ok))
         uexp = (lambda l: self.usu[l][1] if u_role == "loss" else self.us_exp_gp[l])
         if self.usq[7] is not None:       # the only adjoint that does not come out of a conv epilogue
             o.quant_mxfp8(self.us[7], *self.usq[7])
@@ -430,29 +436,57 @@ class NativeCritic:
                 if self.f8 and self.wg8[l] and us_u and self._u_act_live:
                     o.conv_wgrad_f8(cv, self.actu[l - 1][0], self.actu[l - 1][1], self.usu[l][0], uexp(l), P.grad(name).reshape(-1))
                 else:
+                    if l > 0 and not self._act_stored[l - 1]:
+                        raise RuntimeError(f"NativeCritic.backward(wgrad=True): the bf16 weight gradient of layer {l} (features.{2 * l}) would "
+                                           f"read the activation of layer {l - 1}, which the preceding forward did not store: run that "
+                                           "forward with for_wgrad=True")
                     o.conv_wgrad(cv, xin, self.us[l], P.grad(name).reshape(-1), db=P.grad("features.0.bias") if l == 0 else None)
             if l > 0:
                 f8kw = dict(xq=self.usq[l], wq=self.wq_d[l], out_q=self.usq[l - 1]) if self.f8 else {}
                 if us_u and self.usu[l - 1] is not None:
                     f8kw["out_u"] = (self.usu[l - 1][0], uexp(l - 1))
-                # bf16 adjoint us[l-1]: read only by layer l-1's weight gradient (the next data gradient reads the MXFP8 copy) -- dead when
-                # that is the fp8 kernel, or no weight gradient of this pass's adjoints runs at all (generator iteration)
-                if self.f8 and self.skip_dead and l - 1 >= 1 and self.usq[l - 1] is not None and self.act_bits and o.f8_eligible(cv, "dgrad"):
-                    if u_role == "loss":
-                        dead = (not wgrad) or (self.wg8[l - 1] and us_u and self._u_act_live)
-                    else:       # penalty pass: the tangent weight gradients read the adjoints
-                        dead = self.wg8[l - 1] and us_u and self._tan_exp_ok
-                    if dead:
-                        f8kw["skip_y"] = True
+                if self._adjoint_unread(l - 1, wgrad, u_role):
+                    f8kw["skip_y"] = True
+                self._us_stored[l - 1] = not f8kw.get("skip_y", False)
                 if self.act_bits:
                     o.conv_dgrad(cv, self.us[l], P.wd(name), self.us[l - 1], mask_bits=self.act_bits[l - 1], mask_slope=C_SLOPE, **f8kw)
                 else:
                     o.conv_dgrad(cv, self.us[l], P.wd(name), self.us[l - 1], mask=self.acts[l - 1], mask_slope=C_SLOPE, **f8kw)
             elif dx is not None:
                 o.conv_dgrad(cv, self.us[0], P.wd(name), dx)
-        self._us_live = us_u
         if self.f8 and u_role == "loss" and wgrad:     # (the penalty pass updates after its tangent weight gradients have read the copies)
             self._update_exponents("loss")
+
+    def _adjoint_unread(self, l, wgrad, u_role):
+        """Backward: the bf16 adjoint us[l] (written by layer l + 1's data gradient) is read only by layer l's weight gradient (the
+        next data gradient reads the MXFP8 copy) -- dead when that is the fp8 kernel, or no weight gradient of this pass's adjoints
+        runs at all (generator iteration)."""
+        if not (self.f8 and self.skip_dead and l >= 1 and self.usq[l] is not None and self.act_bits
+                and self.ops.f8_eligible(self.convs[l + 1], "dgrad")):
+            return False
+        if u_role == "loss":
+            return bool((not wgrad) or (self.wg8[l] and self._us_live and self._u_act_live))
+        return bool(self.wg8[l] and self._us_live and self._tan_exp_ok)       # penalty pass: the tangent weight gradients read the adjoints
+
+    def _head_backward(self, y7, us7, dout_values, n_wgrad, uh1, fc1_parked):
+        """Adjoint of _head_forward over len(dout_values) passes of B rows, d out = dout_values[pass]: ``us7`` receives d / d y7, ``uh1``
+        FC1's adjoint rows.  The first ``n_wgrad`` passes accumulate the head's parameter gradients; ``fc1_parked``: FC1's weight
+        gradient is left to fc1_flush."""
+        o, P, B = self.ops, self.P, self.B
+        n = len(dout_values)
+        dout, h1, w = self._dout_all[:n * B], self._h1_all[:n * B], slice(0, n_wgrad * B)
+        dout.zero_()
+        for p, v in enumerate(dout_values):
+            o.fill_col(dout[p * B:(p + 1) * B], 0, v)
+        if n_wgrad:
+            o.linear_dw(dout[w], h1[w], P.grad("classifier.2.weight"), o_real=1, net="C")
+            o.colsum(dout[w], P.grad("classifier.2.bias"))
+        o.linear_dx(dout, P.w2d("classifier.2.weight"), uh1, mask=h1, mask_slope=C_SLOPE, o_real=1, net="C")
+        if n_wgrad:
+            if not fc1_parked:
+                o.linear_dw(uh1[w, :FC_HID_P], y7[w], P.grad("classifier.0.weight"), o_real=FC_HID, net="C")
+            o.colsum(uh1[w], P.grad("classifier.0.bias"))
+        o.linear_dx(uh1[:, :FC_HID_P], P.w2d("classifier.0.weight"), us7, mask=y7, mask_slope=C_SLOPE, o_real=FC_HID, net="C")
 
     def _update_exponents(self, role):
         """After a pass's weight gradients have consumed the uniform-scale copies: the exponents the NEXT pass of the same kind writes
@@ -523,9 +557,13 @@ class NativeCritic:
         t0_census = False                      # l0u: t_0 exists as its uniform-scale copy alone (tq = that copy, the exponents its scale row)
         for l, cv in enumerate(self.convs):
             name = f"features.{2 * l}.weight"
-            if self.f8 and self.wg8[l] and tu is not None and getattr(self, "_us_live", False) and r0 == 0:
+            if self.f8 and self.wg8[l] and tu is not None and self._us_live and r0 == 0:
                 o.conv_wgrad_f8(cv, tu[0], tu[1], self.usu[l][0], self.us_exp_gp[l], P.grad(name).reshape(-1))
             else:
+                if not self._us_stored[l]:
+                    raise RuntimeError(f"NativeCritic.gp_tangent: the bf16 weight gradient of layer {l} (features.{2 * l}) would read the "
+                                       f"adjoint of layer {l}, which the preceding backward did not store: run that backward with "
+                                       "u_role=\"gp\" right before the tangent pass (gp_pass does)")
                 o.conv_wgrad(cv, t, us[l], P.grad(name).reshape(-1))
             if self.f8 and l > 0 and self.tan_exp[l - 1] is not None and tq is not None and not (l == 1 and t0_census):
                 o.block_exp_max(tq[1], self.tan_exp[l - 1])     # t_{l-1}'s copy has been consumed: exponents for the next tangent pass
@@ -542,9 +580,8 @@ class NativeCritic:
             if self.f8 and self.tan_exp[l] is not None and tqn is not None and self._tan_exp_ok:
                 tun = (self._tanu[l & 1][:self.acts[l].numel()].view(self.acts[l].shape), self.tan_exp[l])
                 f8kw["out_u"] = tun
-                if self.skip_dead and bits and l < 7 and self.wg8[l + 1] and getattr(self, "_us_live", False) \
-                        and (o.f8_eligible(cv, "fwd") or (l == 0 and self._l0_f8_out)):
-                    f8kw["skip_y"] = True        # the bf16 tangent: read by the next conv (MXFP8 copy) and layer l + 1's fp8 weight gradient only
+                if self._tangent_unread(l):
+                    f8kw["skip_y"] = True
             if self.l0u and l == 0 and tun is not None and f8kw.get("skip_y") and r0 == 0:
                 f8kw = dict(out_u=tun, out_amax=self._t0_amax, skip_y=True)
                 tqn, t0_census = tun, True
@@ -565,19 +602,21 @@ class NativeCritic:
         o.bias_act(self._th1pre, None, self._th1, mask=h1, mask_slope=C_SLOPE)
         o.linear_dw(self._ones, self._th1, P.grad("classifier.2.weight"), o_real=1, net="C")
 
+    def _tangent_unread(self, l):
+        """Tangent pass, layer l writing the uniform-scale copy of its tangent: the bf16 tangent is read by the next conv (MXFP8
+        copy) and layer l + 1's fp8 weight gradient only."""
+        return bool(self.skip_dead and self._bits_all is not None and l < 7 and self.wg8[l + 1] and self._us_live
+                    and (self.ops.f8_eligible(self.convs[l], "fwd") or (l == 0 and self._l0_f8_out)))
+
     # ---- stacked passes: real | fake | x-hat as one batch of 3B (see __init__) ------------------------------------------
     def _cvn(self, n):
         if n not in self._cv_cache:
             self._cv_cache[n] = [dataclasses.replace(cv, N=n) for cv in self.convs]
         return self._cv_cache[n]
 
-    _cv_cache = None
-
     def forward_stacked(self, x3):
         """critic.py:101-106 on x3 = [real | fake | x-hat] (3B samples, compact or padded NHWC).  Returns out[3B, .] (fp32)."""
         o, P, B = self.ops, self.P, self.B
-        if self._cv_cache is None:
-            self._cv_cache = {}
         cur = x3
         for l, cv in enumerate(self._cvn(3 * B)):
             w, bias = P.w(f"features.{2 * l}.weight"), P.master("features.0.bias") if l == 0 else None
@@ -588,18 +627,7 @@ class NativeCritic:
             else:
                 o.conv_fwd(cv, cur, w, self._acts_all[l], bias=bias, act=C_SLOPE, out_bits=self._bits_all[l])
             cur = self._acts_all[l]
-        y7 = self._acts_all[7].view(3 * B, self.fc_k)
-        self._h1pre_all.zero_()
-        for p in range(3):                                # the split-K FC1 kernel takes up to 32 rows per call
-            rows = slice(p * B, (p + 1) * B)
-            o.linear_fwd(y7[rows], P.w2d("classifier.0.weight"), self._h1pre_all[rows], o_real=FC_HID, net="C")
-        o.bias_act(self._h1pre_all, P.master("classifier.0.bias"), self._h1_all, act=C_SLOPE)
-        self._outpre_all.zero_()
-        for p in range(3):
-            rows = slice(p * B, (p + 1) * B)
-            o.linear_fwd(self._h1_all[rows], P.w2d("classifier.2.weight"), self._outpre_all[rows], o_real=1, net="C")
-        o.bias_act(self._outpre_all, P.master("classifier.2.bias"), self._out_all)
-        return self._out_all
+        return self._head_forward(self._acts_all[7].view(3 * B, self.fc_k), 3)
 
     def backward_stacked(self, x3, dout_values, dx):
         """Adjoint chain of forward_stacked: d out_b = dout_values[pass of b]; parameter gradients from the first TWO passes
@@ -607,17 +635,7 @@ class NativeCritic:
         (wasserstein.py:100-106: g = dC/dx-hat, whose adjoints stay in rows [2B, 3B) for the tangent pass)."""
         o, P, B = self.ops, self.P, self.B
         n3, w2 = 3 * B, slice(0, 2 * B)
-        dout, uh1, h1 = self._dout_all, self._uh1_all, self._h1_all
-        dout.zero_()
-        for p in range(3):
-            o.fill_col(dout[p * B:(p + 1) * B], 0, dout_values[p])
-        y7 = self._acts_all[7].view(n3, self.fc_k)
-        o.linear_dw(dout[w2], h1[w2], P.grad("classifier.2.weight"), o_real=1, net="C")
-        o.colsum(dout[w2], P.grad("classifier.2.bias"))
-        o.linear_dx(dout, P.w2d("classifier.2.weight"), uh1, mask=h1, mask_slope=C_SLOPE, o_real=1, net="C")
-        o.colsum(uh1[w2], P.grad("classifier.0.bias"))
-        o.linear_dx(uh1[:, :FC_HID_P], P.w2d("classifier.0.weight"), self._us_all[7].view(n3, self.fc_k),
-                    mask=y7, mask_slope=C_SLOPE, o_real=FC_HID, net="C")
+        self._head_backward(self._acts_all[7].view(n3, self.fc_k), self._us_all[7].view(n3, self.fc_k), dout_values, 2, self._uh1_all, True)
         cv3, cv2, cv1 = self._cvn(n3), self._cvn(2 * B), self.convs
         for l in range(7, -1, -1):
             name = f"features.{2 * l}.weight"
@@ -664,22 +682,11 @@ class NativeGenerator:
         # wgrad(x := dfake, dy := c30) folded back by wgrad_unswap (dg_repack_conv_weights kind 2 / dg_wgrad_unswap)
         self.cv_c32_bwd = Conv(B, hs, hs, self.np_p, F_, cin_real=n_predictands, cin_alg=n_predictands) if n_predictands <= 2 else None
         P = self.P = ParamStore(ops)
-
-        def addconv(name, cv, dgrad=True):
+        for name, cv, _, _, dgrad in self._conv_layers():
             P.add(name + ".weight", (cv.Cout, 9, cv.Cin))
             P.add(name + ".bias", (cv.Cout,))
             if dgrad:
                 P.conv_dgrad[name + ".weight"] = (cv.Cout, cv.Cin)
-        addconv("conv1", self.cv_conv1, dgrad=False)
-        for i in range(num_res_blocks):
-            for j in range(3):
-                for k in range(1, 6):       # the dense blocks' data gradients run on the stacked packs below, not per conv
-                    addconv(f"res_blocks.{i}.dense_blocks.{j}.b{k}.0", self.cv_b[k - 1], dgrad=False)
-        addconv("conv2", self.cv_conv2)
-        for u in range(num_upsample):
-            addconv(f"upsampling.{3 * u}", self.cv_up[u])
-        addconv("conv3.0", self.cv_c30)
-        addconv("conv3.2", self.cv_c32)
         P.finalize()
         o = ops
         self.ndrb = 3 * num_res_blocks
@@ -707,6 +714,7 @@ class NativeGenerator:
         if self.cv_c32_bwd is not None:
             P.after_refresh.append(lambda: o.repack(P.master("conv3.2.weight").reshape(-1), self._w_c32_bwd, self.np_p, F_, 2))
         self._wq = {}
+        self._vq = None       # MXFP8 forms of the virtual data-gradient packs (f8_bwd): created by the first _rebuild_vpacks
         self._qlast = None
         # Dense-block backward (generator.py:14-41).  Conv k of a block reads slab channels [0, kF), so autograd hands the block
         # five data gradients with 128 reduction channels and k*128 output channels each, the later ones accumulating into the
@@ -727,54 +735,49 @@ class NativeGenerator:
         # bf16 kernel runs.  Bias gradients: column sums of the bf16 adjoint slices.
         self.f8_wg = (self.f8_bwd and bool(getattr(o, "f8_wgrad", False)) and bool(getattr(o, "f8_gwgrad", False)) and F_ == 128 and S % 64 == 0)
         self._slab_u = self._us_u = self._ex = self._eu = self._ex_new = self._eu_new = None
-        self._u_ok = self._u_live = False
+        self._u_ok = False        # `_ex` / `_eu` hold exponents: set at the end of the first backward, never cleared
+        self._u_live = False      # the last saved forward wrote valid uniform-scale slab copies: set by forward(save=True), cleared by backward
         P.after_refresh.append(self._rebuild_vpacks)
         if self.f8:
             P.after_refresh.append(self._requantise_weights)
 
-    def _f8_names(self):
+    def _conv_layers(self):
+        """Every conv of generator.py:56-90 in parameter order: (reference name, Conv, real input channels, real output channels,
+        whether it has a data-gradient weight pack of its own)."""
+        yield "conv1", self.cv_conv1, self.cin, self.F, False
         for i in range(self.nrb):
             for j in range(3):
-                for k in range(1, 6):
-                    yield f"res_blocks.{i}.dense_blocks.{j}.b{k}.0", self.cv_b[k - 1]
-        yield "conv2", self.cv_conv2
-        if self.f8_tail:
-            for u in range(self.nup):
-                yield f"upsampling.{3 * u}", self.cv_up[u]
-            yield "conv3.0", self.cv_c30
+                for k in range(1, 6):       # the dense blocks' data gradients run on the stacked packs (`_vpack`), not per conv
+                    yield f"res_blocks.{i}.dense_blocks.{j}.b{k}.0", self.cv_b[k - 1], k * self.F, self.F, False
+        yield "conv2", self.cv_conv2, self.F, self.F, True
+        for u in range(self.nup):
+            yield f"upsampling.{3 * u}", self.cv_up[u], self.F, 4 * self.F, True
+        yield "conv3.0", self.cv_c30, self.F, self.F, True
+        yield "conv3.2", self.cv_c32, self.F, self.npred, True
 
     def _requantise_weights(self):
+        """MXFP8 forward weight forms of the trunk (Conv.net "G") and, with f8_tail, of the up-sampling tail (Conv.net "T")."""
         o, P = self.ops, self.P
-        for name, cv in self._f8_names():
+        for name, cv, _, _, _ in self._conv_layers():
+            if not (cv.net == "G" or (cv.net == "T" and self.f8_tail)):
+                continue
             if name not in self._wq:
                 self._wq[name] = (o.zeros(cv.Cout * 9, cv.Cin, dtype=torch.uint8), o.zeros(cv.Cout * 9, cv.Cin // 32, dtype=torch.uint8))
             off, n, _ = P.entries[name + ".weight"]
             o.quant_mxfp8(P.shadow[off:off + n].view(cv.Cout * 9, cv.Cin), *self._wq[name])
 
     # ---- state_dict interchange ------------------------------------------------------------------
-    def _conv_names(self):
-        yield "conv1", self.cv_conv1, self.cin, self.F
-        for i in range(self.nrb):
-            for j in range(3):
-                for k in range(1, 6):
-                    yield f"res_blocks.{i}.dense_blocks.{j}.b{k}.0", self.cv_b[k - 1], k * self.F, self.F
-        yield "conv2", self.cv_conv2, self.F, self.F
-        for u in range(self.nup):
-            yield f"upsampling.{3 * u}", self.cv_up[u], self.F, 4 * self.F
-        yield "conv3.0", self.cv_c30, self.F, self.F
-        yield "conv3.2", self.cv_c32, self.F, self.npred
-
     def load_state_dict(self, sd):
         t = lambda a: torch.as_tensor(a, dtype=torch.float32).cpu()
         packed = {}
-        for name, cv, ci, co in self._conv_names():
+        for name, cv, _, _, _ in self._conv_layers():
             packed[name + ".weight"] = layout.pack_conv_weight(t(sd[name + ".weight"]), cv.Cout, cv.Cin, cv.pixel_shuffle)
             packed[name + ".bias"] = layout.pack_bias(t(sd[name + ".bias"]), cv.Cout, cv.pixel_shuffle)
         self.P.load_host(packed)
 
     def unpack(self, host):
         sd = {}
-        for name, cv, ci, co in self._conv_names():
+        for name, cv, ci, co, _ in self._conv_layers():
             sd[name + ".weight"] = layout.unpack_conv_weight(host[name + ".weight"], co, ci, cv.pixel_shuffle)
             sd[name + ".bias"] = layout.unpack_bias(host[name + ".bias"], co, cv.pixel_shuffle)
         return sd
@@ -804,8 +807,6 @@ class NativeGenerator:
             for d in range(self.ndrb):
                 for j in range(5):
                     o.quant_mxfp8(self.vpack(d, j).view(F_ * 9, (5 - j) * F_), *self._vq[d][j])
-
-    _vq = None
 
     # ---- forward -----------------------------------------------------------------------------------
     def _slab(self, d, save):
@@ -1068,6 +1069,8 @@ class TrainEngine:
         self.num_steps = 0
         self.n_real_elems = batch * n_predictands * fine * fine
         self.adam_hp = {}          # id(ParamStore) -> HyperParams whose lr / betas / eps differ from ``hp`` (trainer mirror)
+        self._msssim = {}          # n_valid -> msssim.MsSsim of that batch size (metrics_pass)
+        self.graphs = False        # set by enable_graphs: train_step replays the captured iterations
 
     def _sc(self, name):
         i = self.SCALARS.index(name)
@@ -1141,46 +1144,50 @@ class TrainEngine:
         skip its own, bit-identical ``G(coarse)`` (``generator_iteration(reuse_fake=True)``).
         While the generator's own update is still in flight (data parallel: its gradient all-reduce, enqueued at the end of
         the previous generator iteration), the real-sample pass -- which needs no generator -- runs first and hides it."""
+        o, G = self.ops, self.G
+        if self.stacked:
+            fake = G.forward(coarse, save=save_g)                                  # :35
+            o.gp_interp(fine, fake, alpha, self.xhat, self.real_c, self.fake_c)    # :94 (+ the compact real / fake batches)
+            return self._critic_passes_stacked(apply_update)
+
+        def interp(fake, real_c):
+            """:94 -> the generated batch as the critic reads it"""
+            o.gp_interp(fine, fake, alpha, self.xhat, real_c, self.fake_c)
+            return self.fake_c if self.compact2 else fake
+        if G.P._pending is not None:        # real pass first; :35 then is the first use of G's parameters and completes their update
+            self._critic_passes(fine, lambda: interp(G.forward(coarse, save=save_g), None), apply_update)
+        elif self.compact2:                 # :94, hoisted: it also writes the compact real / fake batches
+            xk = interp(G.forward(coarse, save=save_g), self.real_c)               # :35
+            self._critic_passes(self.real_c, xk, apply_update)
+        else:
+            fake = G.forward(coarse, save=save_g)                                  # :35
+            self._critic_passes(fine, lambda: interp(fake, None), apply_update)
+
+    def _critic_passes(self, xr, xk, apply_update):
+        """wasserstein.py:37-55 on the real batch ``xr`` and the generated batch ``xk`` as the critic reads them, x-hat being in
+        ``self.xhat`` by the time the generated pass starts.  ``xk`` may be a callable that produces both then: it runs after the
+        real pass."""
         o, hp, C, B = self.ops, self.hp, self.C, self.B
         bg = B * self.world
-        if self.stacked:
-            return self._critic_iteration_stacked(coarse, fine, alpha, apply_update, save_g)
-        real_first = self.G.P._pending is not None
-        xr = fine
-        if not real_first:
-            fake = self.G.forward(coarse, save=save_g)            # :35
-            if self.compact2:                                     # :94, hoisted: it also writes the compact real / fake batches
-                o.gp_interp(fine, fake, alpha, self.xhat, self.real_c, self.fake_c)
-                xr = self.real_c
         s0, s1, s2 = (0, 1, 2) if C.fc1_fused else (None, None, None)
         C.P.zero_grad(skip="classifier.0.weight" if C.fc1_fused else None)    # :43 (fc1_flush WRITES that gradient)
         out = C.forward(xr, s0, for_wgrad=True)                   # :37
         o.sum_strided(out, B, out.stride(0), 1.0 / B, self._sc("c_real_mean"))
         C.backward(xr, -1.0 / bg, fc1_slot=s0)                    # d(-mean c_real)
-        if real_first:
-            fake = self.G.forward(coarse, save=save_g)            # :35 (first use of G's parameters completes their update)
-        if real_first or not self.compact2:
-            o.gp_interp(fine, fake, alpha, self.xhat, None, self.fake_c)      # :94
-        xk = self.fake_c if self.compact2 else fake
+        if callable(xk):
+            xk = xk()
         out = C.forward(xk, s1, for_wgrad=True)                   # :38
         o.sum_strided(out, B, out.stride(0), 1.0 / B, self._sc("c_fake_mean"))
         C.backward(xk, 1.0 / bg, fc1_slot=s1)                     # d(+mean c_fake)
         C.gp_pass(self.xhat, self.gbuf, self.vbuf, self.ss, self.coef, self._sc("gp_ret"), hp, bg, fc1_slot=s2)   # :40,:87-117
         if C.fc1_fused:
             C.fc1_flush()
-        self._assert_finite("critic", C.P, [("dC/dx-hat", self.gbuf)])
-        if apply_update:
-            self._allreduce_and_step(C.P, defer=True)             # :52-55 (overlaps with the next generator forward)
-
-    def _critic_iteration_stacked(self, coarse, fine, alpha, apply_update, save_g):
-        """The same iteration with the real, generated and interpolated batch going through the critic as ONE batch of 3B
-        (NativeCritic.forward_stacked / backward_stacked): wasserstein.py:37, :38 and :97 are one forward; the backward of :52
-        through the first two and the autograd.grad of :100-106 through the third are one adjoint chain with per-pass d out."""
-        fake = self.G.forward(coarse, save=save_g)                                    # :35
-        self.ops.gp_interp(fine, fake, alpha, self.xhat, self.real_c, self.fake_c)    # :94 (+ the compact real / fake batches)
-        self._critic_passes_stacked(apply_update)
+        self._critic_update(apply_update)
 
     def _critic_passes_stacked(self, apply_update):
+        """The same passes with the real, generated and interpolated batch (``self.x3``) going through the critic as ONE batch of 3B
+        (NativeCritic.forward_stacked / backward_stacked): wasserstein.py:37, :38 and :97 are one forward; the backward of :52
+        through the first two and the autograd.grad of :100-106 through the third are one adjoint chain with per-pass d out."""
         o, hp, C, B = self.ops, self.hp, self.C, self.B
         bg = B * self.world
         C.P.zero_grad(skip="classifier.0.weight")                                     # :43 (fc1_flush WRITES that gradient)
@@ -1190,9 +1197,12 @@ class TrainEngine:
         C.backward_stacked(self.x3, (-1.0 / bg, 1.0 / bg, 1.0), self.gbuf)            # d(-mean c_real + mean c_fake), dC/dx-hat
         C.gp_tangent(self.gbuf, self.vbuf, self.ss, self.coef, self._sc("gp_ret"), hp, bg, 2 * B, 2)   # :40, :110-117
         C.fc1_flush()
-        self._assert_finite("critic", C.P, [("dC/dx-hat", self.gbuf)])
+        self._critic_update(apply_update)
+
+    def _critic_update(self, apply_update):
+        self._assert_finite("critic", self.C.P, [("dC/dx-hat", self.gbuf)])
         if apply_update:
-            self._allreduce_and_step(C.P, defer=True)                                 # :52-55
+            self._allreduce_and_step(self.C.P, defer=True)        # :52-55 (overlaps with the next generator forward)
 
     def generator_iteration(self, coarse, fine, apply_update=True, reuse_fake=False):
         """wasserstein.py:58-83: g_loss = -mean(C(G(x)))*gamma + content_lambda*L1(G(x), y).
@@ -1204,16 +1214,27 @@ class TrainEngine:
             self.dfake = o.zeros(*self.G.fake.shape)
         G.P.zero_grad()                                           # :65
         fake = G.fake if reuse_fake else G.forward(coarse, save=True)   # :67
-        out = C.forward(self.fake_c if reuse_fake and self.compact2 else fake)    # :68 (the critic iteration's compact copy)
+        xk = self._generator_critic_input(fake, fine, reuse_fake)
+        out = C.forward(xk)                                       # :68
         o.sum_strided(out, B, out.stride(0), 1.0 / B, self._sc("g_c_fake_mean"))
-        C.backward(fake, -hp.gamma / bg, wgrad=False, dx=self.gbuf)            # d(-gamma*mean c_fake)/d fake
+        C.backward(xk, -hp.gamma / bg, wgrad=False, dx=self.gbuf)              # d(-gamma*mean c_fake)/d (the critic's input)
         self._sc("l1_sum").zero_()
-        o.l1(fake, fine, self._sc("l1_sum"), grad=self.dfake, grad_scale=hp.content_lambda / (self.n_real_elems * self.world),
-             addend=self.gbuf)                                    # :78 + losses.py:51-53
+        self._assemble_dfake(fake, fine)
         G.backward(coarse, self.dfake)                            # :80
         self._assert_finite("generator", G.P, [("d loss / d fake", self.dfake)])
         if apply_update:
             self._allreduce_and_step(G.P, defer=True)             # :83 (overlaps with the next critic iteration's real pass)
+
+    def _generator_critic_input(self, fake, fine, reuse_fake):
+        """What the critic reads in the generator iteration (:68): the generated batch, or the critic iteration's compact copy of it."""
+        return self.fake_c if reuse_fake and self.compact2 else fake
+
+    def _assemble_dfake(self, fake, fine):
+        """``self.dfake`` = d g_loss / d fake from ``self.gbuf`` = d(-gamma * mean c_fake) / d (the critic's input), plus the content
+        loss's value into ``l1_sum``."""
+        hp = self.hp
+        self.ops.l1(fake, fine, self._sc("l1_sum"), grad=self.dfake, grad_scale=hp.content_lambda / (self.n_real_elems * self.world),
+                    addend=self.gbuf)                             # :78 + losses.py:51-53
 
     def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
@@ -1254,15 +1275,11 @@ class TrainEngine:
         msssim = None
         H, W = fine.shape[1], fine.shape[2]
         if min(H, W) > 96:
-            if self._msssim is None:
-                self._msssim = {}
             if n not in self._msssim:
                 from .msssim import MsSsim
                 self._msssim[n] = MsSsim(o, n, H, W, c_real=self.G.npred)
             msssim = self._msssim[n](fine[:n], fake[:n], dist=self.dist, world=self.world)
         return {"MAE": d["l1_sum"] / cnt, "MSE": d["sq_sum"] / cnt, "Wass": d["c_real_mean"] - d["c_fake_mean"], "MSSSIM": msssim}
-
-    _msssim = None
 
     # ---- HIP graphs: the ~500 launches of an iteration are captured once and replayed (launch-bound small tiles)
     def enable_graphs(self, coarse, fine):
@@ -1290,8 +1307,6 @@ class TrainEngine:
             self.generator_iteration(self._g_coarse, self._g_fine, apply_update=False, reuse_fake=True)
         self.C.P.zero_grad(); self.G.P.zero_grad()
         self.graphs = True
-
-    graphs = False
 
     def train_step(self, coarse, fine, alpha):
         """loop body of _train_epoch, wasserstein.py:131-147 (metrics pass :140 excluded)."""
@@ -1346,9 +1361,8 @@ class TrainEngineFS(TrainEngine):
         self.real_low = self.fake_low = self.tbuf = None
 
     def critic_iteration(self, coarse, fine, alpha, apply_update=True, save_g=False):
-        """wasserstein_fs.py:28-60."""
-        o, hp, C, B = self.ops, self.hp, self.C, self.B
-        bg = B * self.world
+        """wasserstein_fs.py:28-60: the parent's passes (:43-60) on the high-pass parts."""
+        o = self.ops
         fake = self.G.forward(coarse, save=save_g)                # :36
         o.lowpass5(fake, high=self.fake_high)                     # :37,40
         o.lowpass5(fine, high=self.real_high)                     # :38,41
@@ -1356,44 +1370,23 @@ class TrainEngineFS(TrainEngine):
         if self.stacked:
             return self._critic_passes_stacked(apply_update)
         xr, xk = (self.real_c, self.fake_c) if self.compact2 else (self.real_high, self.fake_high)
-        s0, s1, s2 = (0, 1, 2) if C.fc1_fused else (None, None, None)
-        C.P.zero_grad(skip="classifier.0.weight" if C.fc1_fused else None)    # :49 (fc1_flush WRITES that gradient)
-        out = C.forward(xr, s0, for_wgrad=True)                   # :43
-        o.sum_strided(out, B, out.stride(0), 1.0 / B, self._sc("c_real_mean"))
-        C.backward(xr, -1.0 / bg, fc1_slot=s0)
-        out = C.forward(xk, s1, for_wgrad=True)                   # :44
-        o.sum_strided(out, B, out.stride(0), 1.0 / B, self._sc("c_fake_mean"))
-        C.backward(xk, 1.0 / bg, fc1_slot=s1)
-        C.gp_pass(self.xhat, self.gbuf, self.vbuf, self.ss, self.coef, self._sc("gp_ret"), hp, bg, fc1_slot=s2)
-        if C.fc1_fused:
-            C.fc1_flush()
-        self._assert_finite("critic", C.P, [("dC/dx-hat", self.gbuf)])
-        if apply_update:
-            self._allreduce_and_step(C.P, defer=True)             # :57-60
+        self._critic_passes(xr, xk, apply_update)
 
-    def generator_iteration(self, coarse, fine, apply_update=True, reuse_fake=False):
-        """wasserstein_fs.py:63-92: g_loss = -gamma*mean C(fake_high) + content_lambda*L1(fake_low, real_low); the gradient
-        reaches ``fake`` through both branches: d fake = d_high + low^T(g_L1 - d_high)."""
-        o, hp, C, G, B = self.ops, self.hp, self.C, self.G, self.B
-        bg = B * self.world
-        if self.dfake is None:
-            self.dfake = o.zeros(*self.G.fake.shape)
+    def _generator_critic_input(self, fake, fine, reuse_fake):
+        """wasserstein_fs.py:63-92: g_loss = -gamma*mean C(fake_high) + content_lambda*L1(fake_low, real_low): the critic reads the
+        generated batch's high-pass part, the content loss (_assemble_dfake) the low-pass parts written here."""
+        o = self.ops
         if self.tbuf is None:
             self.real_low, self.fake_low, self.tbuf = (o.zeros(*self.fine_shape) for _ in range(3))
-        G.P.zero_grad()                                           # :70
-        fake = G.fake if reuse_fake else G.forward(coarse, save=True)   # :72
         o.lowpass5(fake, low=self.fake_low, high=self.fake_high)  # :73,76
         o.lowpass5(fine, low=self.real_low)                       # :74
-        out = C.forward(self.fake_high)                           # :79
-        o.sum_strided(out, B, out.stride(0), 1.0 / B, self._sc("g_c_fake_mean"))
-        C.backward(self.fake_high, -hp.gamma / bg, wgrad=False, dx=self.gbuf)  # d(-gamma*mean c_fake)/d fake_high
-        self._sc("l1_sum").zero_()
+        return self.fake_high                                     # :79
+
+    def _assemble_dfake(self, fake, fine):
+        """The gradient reaches ``fake`` through both branches: d fake = d_high + low^T(g_L1 - d_high)."""
+        o, hp = self.ops, self.hp
         o.l1(self.fake_low, self.real_low, self._sc("l1_sum"), grad=self.tbuf,
              grad_scale=hp.content_lambda / (self.n_real_elems * self.world))  # :86
         o.axpby(self.tbuf, self.tbuf, 1.0, self.gbuf, -1.0)        # g_L1 - d_high
         o.lowpass5_adjoint(self.tbuf, self.dfake)
         o.axpby(self.dfake, self.dfake, 1.0, self.gbuf, 1.0)       # + d_high
-        G.backward(coarse, self.dfake)                            # :88
-        self._assert_finite("generator", G.P, [("d loss / d fake", self.dfake)])
-        if apply_update:
-            self._allreduce_and_step(G.P, defer=True)             # :91

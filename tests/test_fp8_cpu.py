@@ -278,6 +278,50 @@ def test_engine_fp8_weight_gradients_after_the_first_pass():
         assert res[False][2][k] == res[True][2][k], k                       # the forward and the penalty's value do not depend on it
 
 
+def test_fp8_backward_refuses_activations_the_forward_did_not_store():
+    """fp8 mode with fp8 weight gradients, exponents in place after two critic iterations: ``C.forward(x)`` (for_wgrad=False) does
+    not store the bf16 activations that only fp8 readers follow, so ``C.backward(x, d)`` (wgrad=True), whose bf16 weight-gradient
+    kernel would read them, raises and names the layer instead of returning gradients of stale buffers; the forward with
+    for_wgrad=True serves it, and the input-gradient-only backward of generator_iteration / gp_pass needs neither."""
+    import pytest
+    from downgan_amd import synthetic
+    from downgan_amd.engine import HyperParams, TrainEngine
+    from downgan_amd.layout import nchw_to_nhwc_padded
+    torch.set_num_threads(4)
+    B, S, F_, cin, nrb = 1, 16, 128, 2, 1
+    ops = EmuOps("f32", f8_critic=True)
+    ops.f8_wgrad = True
+    ops.f8_l0u = False
+    eng = TrainEngine(ops, S, F_, cin, B, HyperParams(batch_size=B), num_res_blocks=nrb)
+    eng.G.load_state_dict(synthetic.generator_params(F_, cin, 2, nrb))
+    eng.C.load_state_dict(synthetic.critic_params(F_, 8 * S, 2))
+    coarse, fine = synthetic.tiles(B, cin, S)
+    xc = nchw_to_nhwc_padded(torch.from_numpy(coarse), 16, torch.float32)
+    xf = nchw_to_nhwc_padded(torch.from_numpy(fine), 16, torch.float32)
+    for it in range(2):
+        eng.critic_iteration(xc, xf, torch.from_numpy(synthetic.alpha(B, it)), apply_update=False)
+    C = eng.C
+    for a in C.acts[:7]:                   # whatever an earlier pass left in the buffers must not reach a gradient
+        a.fill_(float("nan"))
+    C.P.zero_grad()
+    C.forward(xf)
+    with pytest.raises(RuntimeError, match=r"layer \d.*for_wgrad=True"):
+        C.backward(xf, 1.0)
+    C.P.zero_grad()
+    C.forward(xf, for_wgrad=True)
+    C.backward(xf, 1.0)
+    g = C.P.g
+    assert bool(torch.isfinite(g).all())
+    for l in range(8):
+        off, n, _ = C.P.entries[f"features.{2 * l}.weight"]
+        assert float(g[off:off + n].abs().max()) > 0, l
+    for a in C.acts[:7]:
+        a.fill_(float("nan"))
+    C.forward(xf)
+    C.backward(xf, 1.0, wgrad=False, dx=eng.gbuf)          # what generator_iteration and gp_pass do
+    assert bool(torch.isfinite(eng.gbuf).all())
+
+
 def test_first_layer_uniform_scale_output_alone():
     """f8_l0u: once exponents exist, the critic's first layer (critic.py:21-24, 2 -> 128 channels: an 8.6-GB store-bound launch at
     configs[1]) writes ONLY the uniform-scale copy of its output -- no MXFP8 copy, no bf16 tensor -- with the census of magnitudes the

@@ -124,20 +124,25 @@ def test_epoch_loop_checkpoints_both_networks(monkeypatch, tmp_path):
         assert all(torch.equal(a[k], b[k]) for k in a)
 
 
-def test_ragged_last_batch_rebinds_the_engine(monkeypatch):
+@pytest.mark.parametrize("trainer", ["WassersteinGAN", "WassersteinGANFS"])
+def test_ragged_last_batch_rebinds_the_engine(monkeypatch, trainer):
     """A DataLoader's ragged last batch (the reference's own _gp cannot take it: wasserstein.py:110 reshapes with hp.batch_size):
     the mirror re-creates its shape-bound engine for the new batch size and carries the parameters AND both Adam states over, so
     the two steps equal two steps of ONE continuously running optimizer (stage.py:63-64) -- checked against the oracle run the same
-    way, and told apart from an optimizer whose moments restart at the re-bind."""
+    way, and told apart from an optimizer whose moments restart at the re-bind.  The frequency-separation trainer shares the
+    re-bind and is held to the same, against its own oracle."""
     from downgan_amd import backend, synthetic
     from downgan_amd.GAN import losses
     from downgan_amd.GAN.dataloader import NetCDFSR
     from downgan_amd.GAN.wasserstein import WassersteinGAN
+    from downgan_amd.GAN.wasserstein_fs import WassersteinGANFS
     from downgan_amd.networks.critic import Critic
     from downgan_amd.networks.generator import Generator
     from oracle import ref_step
     from oracle.emu_ops import EmuOps
     import downgan_amd.config.hyperparams as hp
+    Trainer, Oracle = {"WassersteinGAN": (WassersteinGAN, ref_step.OracleTrainer),
+                       "WassersteinGANFS": (WassersteinGANFS, ref_step.OracleTrainerFS)}[trainer]
     monkeypatch.setattr(backend, "make_ops", lambda dtype, device: EmuOps("f32"))
     monkeypatch.setattr(losses, "_ops", {})
     monkeypatch.setattr(hp, "batch_size", 2)
@@ -146,7 +151,7 @@ def test_ragged_last_batch_rebinds_the_engine(monkeypatch):
     tc, tf = torch.from_numpy(coarse), torch.from_numpy(fine)
     G, C = Generator(16, 128, 2, 2, num_res_blocks=1), Critic(16, 128, 2)
     sd0 = C.state_dict()
-    tr = WassersteinGAN(G, C)
+    tr = Trainer(G, C)
     tr.log_metrics = False
     alphas = [torch.from_numpy(synthetic.alpha(2, 0)), torch.from_numpy(synthetic.alpha(1, 1))]
     it = iter(alphas)
@@ -164,7 +169,7 @@ def test_ragged_last_batch_rebinds_the_engine(monkeypatch):
     def oracle(reset):
         pg = {k: torch.from_numpy(v) for k, v in synthetic.generator_params(16, 2, 2, 1).items()}
         pc = {k: torch.from_numpy(v) for k, v in synthetic.critic_params(16, 128, 2).items()}
-        orc = ref_step.OracleTrainer(pg, pc, ref_step.HP(batch_size=2), num_res_blocks=1)
+        orc = Oracle(pg, pc, ref_step.HP(batch_size=2), num_res_blocks=1)
         r0 = orc.train_step(tc[:2], tf[:2], alphas[0])
         orc.hp.batch_size = 1                                      # wasserstein.py:110 reads the global batch size
         if reset:
