@@ -147,12 +147,12 @@ class WassersteinGAN:
         o.gp_finish(e.ss, B, B * e.world, e.hp.gp_lambda, 0.0, e.coef, e._sc("gp_ret"))
         return float(e._sc("gp_ret").item())
 
-    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None):
+    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
         ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
-        mode, real as staged and generated as written)."""
+        mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated)."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -164,10 +164,10 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions)
+            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions)
+        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -183,6 +183,13 @@ class WassersteinGAN:
     distribution_q = (0.001, 0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99, 0.999)
     distribution_exceed_q = (0.99, 0.999, 0.9999)
     distribution_results = None  # the last epoch's {"train" / "test": (real, fake) histograms.Histogram} when logged
+    # opt-in: per-gridpoint statistics maps of the same real and generated fields (mean, std, skewness, extremes, exceedance
+    # frequencies, bias / MAE / RMSE / temporal correlation), their summary reported per epoch in summary["maps"]; map_spec None
+    # = gridstats.GridSpec.zscore(n_predictands); map_dir: the maps are saved under <map_dir>/<epoch>/<part>/ as .npy files
+    log_maps = False
+    map_spec = None
+    map_dir = None
+    map_results = None           # the last epoch's {"train" / "test": gridstats.GridMaps} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -201,9 +208,16 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return ValueHistogram(spec, device=dev), ValueHistogram(spec, device=dev)
 
+    def _map_stats(self, fine):
+        from ..gridstats import GridSpec, GridStats
+        spec = self.map_spec if self.map_spec is not None else GridSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return GridStats(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}}), created on first use; {} when none is on."""
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}}), created on first
+        use; {} when none is on."""
         kw = {}
         if self.log_spectra:
             sp = acc.setdefault("spectra", {})
@@ -215,7 +229,22 @@ class WassersteinGAN:
             if part not in d:
                 d[part] = self._dist_pair()
             kw["distributions"] = d[part]
+        if self.log_maps:
+            m = acc.setdefault("maps", {})
+            if part not in m:
+                m[part] = self._map_stats(fine)
+            kw["maps"] = m[part]
         return kw
+
+    def _map_summary(self, part, stats, epoch):
+        """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the GridMaps is
+        kept in ``map_results`` and, with ``map_dir``, saved by the first rank."""
+        maps = stats.reduce_(self.dist).result()
+        self.map_results[part] = maps
+        if self.map_dir is not None and (self.dist is None or self.dist.rank == 0):
+            import os
+            maps.save(os.path.join(self.map_dir, str(epoch), part))
+        return maps.summary()
 
     def _distribution_summary(self, part, pair):
         """The JSON-serialisable summary of an accumulator pair (summed over the data-parallel ranks first): channel names,
@@ -246,7 +275,7 @@ class WassersteinGAN:
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
         log, train_metrics, test_metrics = [], [], []
-        acc = {}                                              # "spectra" / "distributions" -> {"train" / "test": (real, fake)}
+        acc = {}                                              # "spectra" / "distributions" / "maps" -> {"train" / "test": accumulators}
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
@@ -276,7 +305,7 @@ class WassersteinGAN:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
-        if self.log_spectra or self.log_distributions:
+        if self.log_spectra or self.log_distributions or self.log_maps:
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -285,6 +314,9 @@ class WassersteinGAN:
             if self.log_distributions:
                 self.distribution_results = {}
                 summary["distributions"] = {k: self._distribution_summary(k, v) for k, v in acc.get("distributions", {}).items()}
+            if self.log_maps:
+                self.map_results = {}
+                summary["maps"] = {k: self._map_summary(k, v, epoch) for k, v in acc.get("maps", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

@@ -79,6 +79,7 @@ class FiniteBufs(C.Structure):
 EOF_MAX_C, EOF_MAX_K = 8, 64
 RAPSD_MAX_N = 2048
 HIST_MAX_BINS, HIST_MAX_OUT = 4096, EOF_MAX_C + 1
+GRID_MAX_THR = 4
 
 
 class EofFields(C.Structure):
@@ -89,6 +90,12 @@ class EofFields(C.Structure):
 class HistSpec(C.Structure):
     _fields_ = [("nbins", C.c_int), ("speed_u", C.c_int), ("speed_v", C.c_int), ("lo", C.c_float * HIST_MAX_OUT),
                 ("inv_w", C.c_float * HIST_MAX_OUT), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C)]
+
+
+class GridSpec(C.Structure):
+    _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("scale", C.c_float * EOF_MAX_C),
+                ("offset", C.c_float * EOF_MAX_C), ("pivot", C.c_float * HIST_MAX_OUT),
+                ("thr", (C.c_float * GRID_MAX_THR) * HIST_MAX_OUT)]
 
 
 MINMAX_PARTS = 256
@@ -164,8 +171,11 @@ _PROTOS = {
     "dg_hist_ws_bytes": [C.POINTER(EofFields), C.POINTER(HistSpec)],
     "dg_hist": [C.POINTER(EofFields), C.POINTER(HistSpec), _vp, _vp, _vp, _vp, _vp],
     "dg_hist_host_bins": [C.POINTER(HistSpec), _vp, _i, _i64, _vp],
+    "dg_gridstats_ws_bytes": [C.POINTER(EofFields), _i, C.POINTER(GridSpec)],
+    "dg_gridstats_slices": [_i, _i],
+    "dg_gridstats": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(GridSpec), _vp, _vp, _vp, _vp, _vp],
 }
-_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

@@ -14,13 +14,13 @@
 #include <math.h>
 
 #include "dg_internal.h"
+#include "hist_common.h"
 
 namespace {
 
 constexpr int HIST_THREADS = 256;
 constexpr int HIST_GRID_MAX = 2048;                   // workgroups per launch (memory-bound: cap and grid-stride)
 constexpr long long HIST_ITEMS_MAX = 1LL << 20;       // items per thread per launch: <= 2^30 values per workgroup, no uint32 wrap
-constexpr int HIST_NCHW4 = 0, HIST_PIX16 = 1, HIST_ANY = 2;
 constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT;
 
 struct HistArgs {
@@ -35,18 +35,7 @@ struct HistArgs {
   float* part_e;              // [grid][MAXO][2]
 };
 
-// Definition, shared by the kernels and the host reference: each line is one correctly rounded fp32 operation.
-__host__ __device__ inline float hist_affine(float x, float scale, float offset) {
-#pragma clang fp contract(off)
-  const float m = x * scale;
-  return m + offset;
-}
-__host__ __device__ inline float hist_speed(float u, float v) {
-#pragma clang fp contract(off)
-  const float uu = u * u;
-  const float vv = v * v;
-  return __builtin_sqrtf(uu + vv);
-}
+// The bin rule of the definition (hist_affine and hist_speed: hist_common.h): each line is one correctly rounded fp32 operation.
 __host__ __device__ inline int hist_bin(float y, float lo, float inv_w, int nbins) {
 #pragma clang fp contract(off)
   const float d = y - lo;
@@ -228,19 +217,6 @@ bool spec_ok(const dg_hist_spec* s, int C) {
   return true;
 }
 
-bool fields_ok(const dg_eof_fields* x) {
-  return x && x->base && x->T >= 1 && x->C >= 1 && x->C <= MAXC && x->P >= 1 && x->ld_t >= 0 && x->ld_c >= 0 && x->ld_p >= 0;
-}
-
-int hist_mode(const dg_eof_fields* x) {
-  const size_t es = x->dtype == DG_F32 ? 4 : 2;
-  const uintptr_t b = reinterpret_cast<uintptr_t>(x->base);
-  if (x->ld_p == 1 && x->P % 4 == 0 && x->ld_t % 4 == 0 && x->ld_c % 4 == 0 && b % (4 * es) == 0) return HIST_NCHW4;
-  if (x->ld_c == 1 && x->ld_p * es >= 16 && (x->ld_p * es) % 16 == 0 && (size_t)x->C * es <= 16 && (x->ld_t * es) % 16 == 0 && b % 16 == 0)
-    return HIST_PIX16;
-  return HIST_ANY;
-}
-
 int hist_grid(long long items) {
   const long long g = (items + HIST_THREADS - 1) / HIST_THREADS;
   return (int)(g < 1 ? 1 : g > HIST_GRID_MAX ? HIST_GRID_MAX : g);
@@ -256,7 +232,7 @@ int launch(const HistArgs& a, int grid, size_t lds, hipStream_t st) {
 }  // namespace
 
 extern "C" size_t dg_hist_ws_bytes(const dg_eof_fields* x, const dg_hist_spec* s) {
-  if (!fields_ok(x) || !spec_ok(s, x->C)) return 0;
+  if (!hist_fields_ok(x) || !spec_ok(s, x->C)) return 0;
   return (size_t)HIST_GRID_MAX * MAXO * 2 * (sizeof(double) + sizeof(float));
 }
 
@@ -278,7 +254,7 @@ extern "C" int dg_hist_host_bins(const dg_hist_spec* s, const float* x, int C, i
 
 extern "C" int dg_hist(const dg_eof_fields* x, const dg_hist_spec* s, void* ws, int64_t* counts, double* moments, float* extrema,
                        void* stream) {
-  if (!fields_ok(x) || !spec_ok(s, x->C) || !ws || !counts || !moments || !extrema) return DG_ERR_BAD_SHAPE;
+  if (!hist_fields_ok(x) || !spec_ok(s, x->C) || !ws || !counts || !moments || !extrema) return DG_ERR_BAD_SHAPE;
   if (x->dtype != DG_F32 && x->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
   const int mode = hist_mode(x);
   const int speed = s->speed_u >= 0 ? 1 : 0, nout = x->C + speed;

@@ -882,6 +882,31 @@ class HipOps:
         check(self.lib.dg_hist(C.byref(f), C.byref(spec), _ptr(ws), _ptr(counts), _ptr(moments), _ptr(extrema), self._stream()),
               "dg_hist")
 
+    # ------------------------------------------------------------------ per-gridpoint statistics (csrc/gridstats.hip)
+    def gridstats_ws_bytes(self, f, paired, spec):
+        """Workspace bytes of one dg_gridstats call over the descriptor ``f`` (one series, or with ``paired`` two) with the
+        _lib.GridSpec ``spec`` (0: invalid)."""
+        return int(self.lib.dg_gridstats_ws_bytes(C.byref(f), 1 if paired else 0, C.byref(spec)))
+
+    def gridstats(self, fa, fb, spec, sums, extrema, counts):
+        """Accumulate the per-pixel statistics of the fields of ``fa`` (eof_fields; with ``fb`` not None: of the pair fa, fb)
+        under ``spec`` (_lib.GridSpec): sums fp64 [nout, 4 | 12, P] +=, extrema fp32 [nout, 2 | 4, P] min / max, counts int32
+        [nout, 1 + nthr | 3 + 2 nthr, P] += (rows: include/downgan_hip.h).  The workspace is cached on this object."""
+        paired = fb is not None
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        rows = (12, 4, 3 + 2 * spec.nthr) if paired else (4, 2, 1 + spec.nthr)
+        for out, dt, r in ((sums, torch.float64, rows[0]), (extrema, torch.float32, rows[1]), (counts, torch.int32, rows[2])):
+            assert out.dtype == dt and out.is_contiguous() and out.numel() == nout * r * fa.P and out.is_cuda, (out.dtype, out.shape)
+        assert not paired or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.gridstats_ws_bytes(fa, paired, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, spec.nthr)
+        ws = getattr(self, "_grid_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._grid_ws = ws = None
+            self._grid_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_gridstats(C.byref(fa), C.byref(fb) if paired else None, C.byref(spec), _ptr(ws), _ptr(sums),
+                                    _ptr(extrema), _ptr(counts), self._stream()), "dg_gridstats")
+
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32
         check(self.lib.dg_sum_strided(_ptr(inp), n, stride, float(scale), _ptr(out), self._stream()), "dg_sum_strided")

@@ -550,6 +550,48 @@ int dg_hist(const dg_eof_fields* x, const dg_hist_spec* s, void* ws, int64_t* co
             void* stream);
 int dg_hist_host_bins(const dg_hist_spec* s, const float* x, int C, int64_t n, int32_t* bins);
 
+/* ---- Per-gridpoint statistics (csrc/gridstats.hip) -----------------------------------------------------------------------
+ * Where on the grid is the generator wrong: running per-pixel statistics over the fields t of one series a, or of two series
+ * a (real) and b (generated) of equal T, C, P, each read in place through the EOF descriptor (NCHW fp32 / bf16, the resident
+ * feed's [n, H, W, c] store, the generator's padded NHWC output; a and b may differ in layout and dtype).  The output values
+ * are those of the value histograms (the same code, csrc/hist_common.h), every fp32 operation rounded once, never contracted:
+ *   y_c = (x_c * scale[c]) + offset[c]                     output channel j = c
+ *   s   = sqrt(y_u * y_u + y_v * y_v)                       speed_u >= 0: appended as output channel C (nout = C + 1)
+ *   valid <=> y finite;   u = (double)y - (double)pivot[j]
+ * Per series, over the valid t of output channel j and pixel p: n (int32), S1..S4 = sum u, u^2, u^3, u^4 (fp64), min and max
+ * of y (fp32), and over ALL t the exceedance counts E_k = #{y > thr[j][k]}, k < nthr (an fp32 compare: NaN is false, +inf is
+ * true).  Paired, over the t where both values are valid: n_ab, D1 = sum d, DA = sum |d|, D2 = sum d^2 with
+ * d = (double)y_b - (double)y_a, and X = sum u_a u_b.
+ * Everything ACCUMULATES into caller-owned device arrays, the pixel index fastest (the caller initialises them: zeros, and
+ * +inf / -inf for the minima / maxima).  Rows per output channel:
+ *   sums    fp64  [nout][NS][P]   one series (NS = 4):  S1 S2 S3 S4
+ *                                 paired    (NS = 12): a.S1 a.S2 a.S3 a.S4  b.S1 b.S2 b.S3 b.S4  D1 DA D2 X
+ *   extrema fp32  [nout][NE][P]   one series (NE = 2):  min max;   paired (NE = 4): a.min a.max b.min b.max
+ *   counts  int32 [nout][NC][P]   one series (NC = 1 + nthr):      n  E_0 .. E_{nthr-1}
+ *                                 paired    (NC = 3 + 2 nthr):     n_a n_b n_ab  a.E_0 .. a.E_{nthr-1}  b.E_0 .. b.E_{nthr-1}
+ * A thread owns its pixels and walks the fields in t order with its state in registers, so there are no atomics at all: the
+ * integer counts and the extrema are exact, and two calls on the same data are bit-identical.  When P alone does not fill the
+ * chip the t range is cut into S = dg_gridstats_slices(T, P) contiguous slices, slice s = fields [s T / S, (s + 1) T / S);
+ * each slice's partial state goes to the workspace and a second kernel adds the slices in slice order into the accumulators.
+ * The bits of the fp64 sums therefore depend on S, a function of (T, P) only:
+ *   nb = ceil(P / 256);   S = 1 when nb >= 1024, else max(1, min(ceil(1024 / nb), floor(T / 16))).
+ *
+ * dg_gridstats_ws_bytes: workspace bytes of one call (0 for an invalid descriptor or spec; `paired` != 0: two series).
+ * dg_gridstats_slices: host-side, the S above (0 for T < 1 or P < 1).
+ * dg_gridstats: b NULL = one series.  ws may be NULL when S = 1. */
+#define DG_GRID_MAX_THR 4
+typedef struct dg_grid_spec {
+  int speed_u, speed_v;            /* input channels of the speed channel, or -1, -1: none */
+  int nthr;                        /* 0 .. DG_GRID_MAX_THR thresholds per output channel */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float pivot[DG_HIST_MAX_OUT];    /* per output channel, finite */
+  float thr[DG_HIST_MAX_OUT][DG_GRID_MAX_THR];       /* per output channel, the first nthr finite */
+} dg_grid_spec;
+size_t dg_gridstats_ws_bytes(const dg_eof_fields* a, int paired, const dg_grid_spec* s);
+int dg_gridstats_slices(int T, int P);
+int dg_gridstats(const dg_eof_fields* a, const dg_eof_fields* b, const dg_grid_spec* s, void* ws, double* sums, float* extrema,
+                 int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
