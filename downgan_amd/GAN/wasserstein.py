@@ -147,12 +147,13 @@ class WassersteinGAN:
         o.gp_finish(e.ss, B, B * e.world, e.hp.gp_lambda, 0.0, e.coef, e._sc("gp_ret"))
         return float(e._sc("gp_ret").item())
 
-    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None):
+    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
         ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
-        mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated)."""
+        mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
+        ``fss``: one ``fss.FractionsSkill`` fed the same pair."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -164,10 +165,10 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps)
+            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps)
+        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -190,6 +191,11 @@ class WassersteinGAN:
     map_spec = None
     map_dir = None
     map_results = None           # the last epoch's {"train" / "test": gridstats.GridMaps} when logged
+    # opt-in: the fractions skill score of the same (real, generated) pairs per threshold and neighbourhood size (exact integer
+    # sums on the device), its summary reported per epoch in summary["fss"]; fss_spec None = fss.FssSpec.zscore(n_predictands)
+    log_fss = False
+    fss_spec = None
+    fss_results = None           # the last epoch's {"train" / "test": fss.FssResult} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -214,9 +220,15 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return GridStats(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
 
+    def _fss_acc(self, fine):
+        from ..fss import FractionsSkill, FssSpec
+        spec = self.fss_spec if self.fss_spec is not None else FssSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return FractionsSkill(spec, fine.shape[-2], fine.shape[-1], device=dev)
+
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -234,7 +246,19 @@ class WassersteinGAN:
             if part not in m:
                 m[part] = self._map_stats(fine)
             kw["maps"] = m[part]
+        if self.log_fss:
+            f = acc.setdefault("fss", {})
+            if part not in f:
+                f[part] = self._fss_acc(fine)
+            kw["fss"] = f[part]
         return kw
+
+    def _fss_summary(self, part, acc):
+        """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
+        FssResult is kept in ``fss_results``."""
+        res = acc.reduce_(self.dist).result()
+        self.fss_results[part] = res
+        return res.summary()
 
     def _map_summary(self, part, stats, epoch):
         """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the GridMaps is
@@ -275,7 +299,7 @@ class WassersteinGAN:
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
         log, train_metrics, test_metrics = [], [], []
-        acc = {}                                              # "spectra" / "distributions" / "maps" -> {"train" / "test": accumulators}
+        acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" -> {"train" / "test": accumulators}
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
@@ -305,7 +329,7 @@ class WassersteinGAN:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
-        if self.log_spectra or self.log_distributions or self.log_maps:
+        if self.log_spectra or self.log_distributions or self.log_maps or self.log_fss:
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -317,6 +341,9 @@ class WassersteinGAN:
             if self.log_maps:
                 self.map_results = {}
                 summary["maps"] = {k: self._map_summary(k, v, epoch) for k, v in acc.get("maps", {}).items()}
+            if self.log_fss:
+                self.fss_results = {}
+                summary["fss"] = {k: self._fss_summary(k, v) for k, v in acc.get("fss", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

@@ -80,6 +80,7 @@ EOF_MAX_C, EOF_MAX_K = 8, 64
 RAPSD_MAX_N = 2048
 HIST_MAX_BINS, HIST_MAX_OUT = 4096, EOF_MAX_C + 1
 GRID_MAX_THR = 4
+FSS_MAX_THR, FSS_MAX_SCALES, FSS_MAX_SIDE = 4, 8, 2048
 
 
 class EofFields(C.Structure):
@@ -96,6 +97,12 @@ class GridSpec(C.Structure):
     _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("scale", C.c_float * EOF_MAX_C),
                 ("offset", C.c_float * EOF_MAX_C), ("pivot", C.c_float * HIST_MAX_OUT),
                 ("thr", (C.c_float * GRID_MAX_THR) * HIST_MAX_OUT)]
+
+
+class FssSpec(C.Structure):
+    _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("nscale", C.c_int),
+                ("win", C.c_int * FSS_MAX_SCALES), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
+                ("thr", (C.c_float * FSS_MAX_THR) * HIST_MAX_OUT)]
 
 
 MINMAX_PARTS = 256
@@ -174,8 +181,13 @@ _PROTOS = {
     "dg_gridstats_ws_bytes": [C.POINTER(EofFields), _i, C.POINTER(GridSpec)],
     "dg_gridstats_slices": [_i, _i],
     "dg_gridstats": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(GridSpec), _vp, _vp, _vp, _vp, _vp],
+    "dg_fss_ws_bytes": [C.POINTER(EofFields), _i, _i, C.POINTER(FssSpec)],
+    "dg_fss": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(FssSpec), _vp, _vp, _vp, _vp, _vp],
+    "dg_fss_host": [C.POINTER(FssSpec), _vp, _vp, _i, _i, _i, _vp, _vp],
+    "dg_fss_bound": [_i, _i, _i],
 }
-_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
+             "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

@@ -1236,7 +1236,7 @@ class TrainEngine:
         self.ops.l1(fake, fine, self._sc("l1_sum"), grad=self.dfake, grad_scale=hp.content_lambda / (self.n_real_elems * self.world),
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
-    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None):
+    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1250,7 +1250,9 @@ class TrainEngine:
         in bf16 mode the staged real fields and the generated ones are bf16 (spacing 0.031 on [4, 8), coarser than the default
         bin width of 0.0098), so the histograms are those of the bf16 values.
         ``maps``: a paired ``gridstats.GridStats`` that receives (fine[:n], fake[:n]) in one call: the per-gridpoint statistics
-        of both series and of their difference."""
+        of both series and of their difference.
+        ``fss``: a ``fss.FractionsSkill`` that likewise receives (fine[:n], fake[:n]) in one call: the fractions skill score's
+        exact sums of the pair."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1267,6 +1269,8 @@ class TrainEngine:
             distributions[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if maps is not None:
             maps.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if fss is not None:
+            fss.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

@@ -907,6 +907,31 @@ class HipOps:
         check(self.lib.dg_gridstats(C.byref(fa), C.byref(fb) if paired else None, C.byref(spec), _ptr(ws), _ptr(sums),
                                     _ptr(extrema), _ptr(counts), self._stream()), "dg_gridstats")
 
+    # ------------------------------------------------------------------ fractions skill score (csrc/fss.hip)
+    def fss_ws_bytes(self, f, H, W, spec):
+        """Workspace bytes of one dg_fss call over the descriptor ``f`` (either series) of H x W fields with the _lib.FssSpec
+        ``spec`` (0: invalid, or more fields than one call may take: T * max dg_fss_bound > 2^62)."""
+        return int(self.lib.dg_fss_ws_bytes(C.byref(f), int(H), int(W), C.byref(spec)))
+
+    def fss(self, fa, fb, H, W, spec, sums, rates, per_field=None):
+        """Accumulate the fractions-skill-score integers of the pair of series ``fa`` (real), ``fb`` (generated) (eof_fields,
+        H x W fields) under ``spec`` (_lib.FssSpec): sums int64 [nout, nthr, nscale, 3] (D A B) +=, rates int64 [nout, nthr, 2]
+        (N_a N_b) +=, per_field int64 [T, nout, nthr, nscale, 3] overwritten when given.  The workspace is cached on this
+        object."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        n = nout * spec.nthr * spec.nscale * 3
+        for out, m in ((sums, n), (rates, nout * spec.nthr * 2), (per_field, fa.T * n)):
+            assert out is None or (out.dtype == torch.int64 and out.is_contiguous() and out.numel() == m and out.is_cuda), (m,)
+        assert (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.fss_ws_bytes(fa, H, W, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, H, W, spec.nthr, spec.nscale)
+        ws = getattr(self, "_fss_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._fss_ws = ws = None
+            self._fss_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_fss(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(sums), _ptr(rates),
+                              _ptr(per_field), self._stream()), "dg_fss")
+
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32
         check(self.lib.dg_sum_strided(_ptr(inp), n, stride, float(scale), _ptr(out), self._stream()), "dg_sum_strided")

@@ -592,6 +592,53 @@ int dg_gridstats_slices(int T, int P);
 int dg_gridstats(const dg_eof_fields* a, const dg_eof_fields* b, const dg_grid_spec* s, void* ws, double* sums, float* extrema,
                  int32_t* counts, void* stream);
 
+/* ---- Fractions skill score (csrc/fss.hip) -----------------------------------------------------------------------------------
+ * At which neighbourhood size does the generated field put threshold exceedances where the real field has them (Roberts & Lean
+ * 2008): the score that does not punish a displaced feature twice.  Fields are H x W, read through the EOF descriptor with
+ * P = H*W, p = h*W + w; series a (real) and b (generated) have equal T, C, P and may differ in layout and dtype (NCHW fp32 /
+ * bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC output).  The output values y are those of the
+ * value histograms and the per-gridpoint statistics (the same code, csrc/hist_common.h): C components plus the optional speed
+ * channel appended last (nout = C + 1).  For output channel j, threshold k (thr[j][k], fp32) and window side n = win[s] (odd):
+ *   masks          I_a[t,p] = (y_a > thr[j][k]), an fp32 compare: NaN is false, +inf is true, equality is false; I_b likewise
+ *   window counts  c_a[t,h,w] = number of set I_a in rows h-r .. h+r, columns w-r .. w+r, r = (n-1)/2; positions outside the
+ *                  grid count zero (zero padding); c_b likewise
+ *   sums           D = sum (c_a - c_b)^2,  A = sum c_a^2,  B = sum c_b^2   over all t and pixels, exact integers
+ *   base rates     N_a = sum I_a,  N_b = sum I_b
+ *   score          FSS = 1 - D / (A + B) (the 1/n^2 of the fractions cancels; NaN when A + B = 0), formed on the host from the
+ *                  integers
+ * One kernel reads every pixel of a series once, forms the masks of all (j, k) and writes their row prefix counts (wave ballots
+ * and popcounts) into one uint32 plane per (t, series, j, k) of the workspace; a second accumulates the planes down the columns
+ * into summed-area tables (entries <= P <= 2^22); a third takes the four clipped corners of both tables per pixel and scale,
+ * squares in 64-bit, reduces per workgroup and adds with 64-bit integer atomics into per-field slots of the workspace; the last
+ * adds the slots to the accumulators.  No float after the compare and only integer atomics: the results are exact and two calls
+ * on the same data are bit-identical.
+ *
+ * dg_fss_bound: host-side, H*W * (min(win, H) * min(win, W))^2, the most one field adds to D, A or B; 0 when H, W or win is
+ *   invalid or the value exceeds 2^62.
+ * dg_fss_ws_bytes: workspace bytes of one call (0 for an invalid descriptor, grid or spec): 8 nout nthr P bytes per field plus
+ *   the per-field slots.
+ * dg_fss: sums int64 [nout][nthr][nscale][3] (D A B) and rates int64 [nout][nthr][2] (N_a N_b) ACCUMULATE (the caller zeroes
+ *   them and owns their headroom); per_field int64 [T][nout][nthr][nscale][3] is overwritten and may be NULL.  Rejected before
+ *   any launch: descriptors that differ in T / C / P, P != H*W, H or W above DG_FSS_MAX_SIDE, an even, unsorted or out-of-range
+ *   win, a non-finite thr / scale / offset, a scale whose dg_fss_bound is 0, and T * max_s dg_fss_bound > 2^62 (one call cannot
+ *   overflow).
+ * dg_fss_host: host-side, the same definition for one field pair, planar fp32 [C][H][W]; sums and rates +=. */
+#define DG_FSS_MAX_THR 4
+#define DG_FSS_MAX_SCALES 8
+#define DG_FSS_MAX_SIDE 2048            /* H, W */
+typedef struct dg_fss_spec {
+  int speed_u, speed_v;                 /* input channels of the speed channel, or -1, -1: none */
+  int nthr, nscale;                     /* 1 .. MAX each */
+  int win[DG_FSS_MAX_SCALES];           /* odd, 1 <= win <= 2*DG_FSS_MAX_SIDE - 1, strictly increasing */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float thr[DG_HIST_MAX_OUT][DG_FSS_MAX_THR];        /* per output channel, the first nthr finite */
+} dg_fss_spec;
+size_t dg_fss_ws_bytes(const dg_eof_fields* a, int H, int W, const dg_fss_spec* s);
+int dg_fss(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_fss_spec* s, void* ws, int64_t* sums,
+           int64_t* rates, int64_t* per_field, void* stream);
+int dg_fss_host(const dg_fss_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* sums, int64_t* rates);
+int64_t dg_fss_bound(int H, int W, int win);
+
 #ifdef __cplusplus
 }
 #endif
