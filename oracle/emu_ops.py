@@ -502,6 +502,9 @@ class EmuOps:
         buf[:, col] = value
 
     def adam(self, p, g, m, v, shadow, lr, beta1, beta2, eps, step, grad_scale=1.0):
+        # dg_adam takes its hyper-parameters as fp32 and forms 1 - beta from the ROUNDED beta (exact in fp32): 1 - fp32(0.99) is
+        # 1e-6 (17 fp32 ulps) away from the fp32 nearest to 0.01, which a per-element comparison of v sees
+        lr, beta1, beta2, eps = (float(torch.tensor(float(x), dtype=torch.float32)) for x in (lr, beta1, beta2, eps))
         gg = g * grad_scale
         m.mul_(beta1).add_(gg, alpha=1 - beta1)
         v.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
