@@ -147,13 +147,13 @@ class WassersteinGAN:
         o.gp_finish(e.ss, B, B * e.world, e.hp.gp_lambda, 0.0, e.coef, e._sc("gp_ret"))
         return float(e._sc("gp_ret").item())
 
-    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None):
+    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
         ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
         mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
-        ``fss``: one ``fss.FractionsSkill`` fed the same pair."""
+        ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -165,10 +165,10 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss)
+            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss)
+        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -196,6 +196,12 @@ class WassersteinGAN:
     log_fss = False
     fss_spec = None
     fss_results = None           # the last epoch's {"train" / "test": fss.FssResult} when logged
+    # opt-in: joint histograms of the same (real, generated) pairs -- wind roses, (u, v) densities and real-vs-generated densities
+    # (exact integer tables on the device), their summary reported per epoch in summary["joint"]; joint_spec None =
+    # joint.JointSpec.zscore(n_predictands)
+    log_joint = False
+    joint_spec = None
+    joint_results = None         # the last epoch's {"train" / "test": joint.Joint} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -226,9 +232,15 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return FractionsSkill(spec, fine.shape[-2], fine.shape[-1], device=dev)
 
+    def _joint_acc(self):
+        from ..joint import JointSpec, ValueJoint
+        spec = self.joint_spec if self.joint_spec is not None else JointSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return ValueJoint(spec, device=dev)
+
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -251,7 +263,19 @@ class WassersteinGAN:
             if part not in f:
                 f[part] = self._fss_acc(fine)
             kw["fss"] = f[part]
+        if self.log_joint:
+            j = acc.setdefault("joint", {})
+            if part not in j:
+                j[part] = self._joint_acc()
+            kw["joint"] = j[part]
         return kw
+
+    def _joint_summary(self, part, acc):
+        """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
+        Joint is kept in ``joint_results``."""
+        res = acc.reduce_(self.dist).result()
+        self.joint_results[part] = res
+        return res.summary()
 
     def _fss_summary(self, part, acc):
         """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
@@ -299,7 +323,7 @@ class WassersteinGAN:
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
         log, train_metrics, test_metrics = [], [], []
-        acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" -> {"train" / "test": accumulators}
+        acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" / "joint" -> {"train" / "test": accumulators}
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
@@ -329,7 +353,7 @@ class WassersteinGAN:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
-        if self.log_spectra or self.log_distributions or self.log_maps or self.log_fss:
+        if self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint:
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -344,6 +368,9 @@ class WassersteinGAN:
             if self.log_fss:
                 self.fss_results = {}
                 summary["fss"] = {k: self._fss_summary(k, v) for k, v in acc.get("fss", {}).items()}
+            if self.log_joint:
+                self.joint_results = {}
+                summary["joint"] = {k: self._joint_summary(k, v) for k, v in acc.get("joint", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

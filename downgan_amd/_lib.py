@@ -81,6 +81,7 @@ RAPSD_MAX_N = 2048
 HIST_MAX_BINS, HIST_MAX_OUT = 4096, EOF_MAX_C + 1
 GRID_MAX_THR = 4
 FSS_MAX_THR, FSS_MAX_SCALES, FSS_MAX_SIDE = 4, 8, 2048
+HIST2D_MAX_PAIRS, HIST2D_MAX_CELLS, HIST2D_MAX_SECTORS = 8, 16384, 72
 
 
 class EofFields(C.Structure):
@@ -103,6 +104,16 @@ class FssSpec(C.Structure):
     _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("nscale", C.c_int),
                 ("win", C.c_int * FSS_MAX_SCALES), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
                 ("thr", (C.c_float * FSS_MAX_THR) * HIST_MAX_OUT)]
+
+
+class Hist2dAxis(C.Structure):
+    _fields_ = [("src", C.c_int), ("chan", C.c_int), ("nbins", C.c_int), ("lo", C.c_float), ("inv_w", C.c_float)]
+
+
+class Hist2dSpec(C.Structure):
+    _fields_ = [("npairs", C.c_int), ("speed_u", C.c_int), ("speed_v", C.c_int), ("nsec", C.c_int), ("calm", C.c_float),
+                ("tan_k", C.c_float * (HIST2D_MAX_SECTORS // 4)), ("scale", C.c_float * EOF_MAX_C),
+                ("offset", C.c_float * EOF_MAX_C), ("ax", (Hist2dAxis * 2) * HIST2D_MAX_PAIRS)]
 
 
 MINMAX_PARTS = 256
@@ -185,9 +196,12 @@ _PROTOS = {
     "dg_fss": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(FssSpec), _vp, _vp, _vp, _vp, _vp],
     "dg_fss_host": [C.POINTER(FssSpec), _vp, _vp, _i, _i, _i, _vp, _vp],
     "dg_fss_bound": [_i, _i, _i],
+    "dg_hist2d_ws_bytes": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(Hist2dSpec)],
+    "dg_hist2d": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(Hist2dSpec), _vp, _vp, _vp],
+    "dg_hist2d_host_bins": [C.POINTER(Hist2dSpec), _vp, _vp, _i, _i64, _vp],
 }
 _RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
-             "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64}      # every other entry point returns a dg_status
+             "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

@@ -1,5 +1,5 @@
-// The value transform and the load-mode rule shared by the value histograms (histogram.hip) and the per-gridpoint statistics
-// (gridstats.hip): both read fields through dg_eof_fields and must see the same output values y bit for bit.
+// The value transform, the bin rules and the load-mode rule shared by the value histograms (histogram.hip), the per-gridpoint
+// statistics (gridstats.hip) and the joint histograms (joint.hip): all read fields through dg_eof_fields and must see the same output values y bit for bit.
 #pragma once
 #include <stdint.h>
 
@@ -16,6 +16,35 @@ __host__ __device__ inline float hist_speed(float u, float v) {
   const float uu = u * u;
   const float vv = v * v;
   return __builtin_sqrtf(uu + vv);
+}
+// The bin rule of the definition: each line is one correctly rounded fp32 operation.
+__host__ __device__ inline int hist_bin(float y, float lo, float inv_w, int nbins) {
+#pragma clang fp contract(off)
+  const float d = y - lo;
+  const float t = d * inv_w;
+  const int b = t < 0.f ? 0 : t >= (float)nbins ? nbins + 1 : 1 + (int)t;   // selects, not branches
+  return t != t ? nbins + 2 : b;
+}
+// The direction rule of the joint histograms (include/downgan_hip.h "Joint histograms", steps 1-8): the index of the sector the
+// wind (yu, yv) of speed s comes from; K = nsec / 4, tan_k[k] = fp32(tan(k pi / (4 K))), k = 1 .. K-1.  No atan2: compares of
+// one rounded product each.
+__host__ __device__ inline int hist_dir(float yu, float yv, float s, float calm, int K, const float* tan_k) {
+#pragma clang fp contract(off)
+  if (yu != yu || yv != yv) return 4 * K + 2;
+  if (!(s > calm)) return 0;
+  const float x = -yu, y = -yv;
+  const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+  const bool swap = ax > ay;
+  const float m = swap ? ay : ax, M = swap ? ax : ay;
+  int j = 0;
+  for (int k = 1; k < K; ++k) {
+    const float e = M * tan_k[k];
+    j += m >= e ? 1 : 0;
+  }
+  const int q = swap ? 2 * K - 1 - j : j;
+  const int h = x >= 0.f && y > 0.f ? q : x > 0.f && y <= 0.f ? 4 * K - 1 - q : x <= 0.f && y < 0.f ? 4 * K + q : 8 * K - 1 - q;
+  const int sec = (h + 1) >> 1;
+  return 1 + (sec >= 4 * K ? sec - 4 * K : sec);
 }
 
 // Load modes: HIST_NCHW4 = four consecutive pixels of one NCHW plane per load (16 B fp32, 8 B bf16); HIST_PIX16 = one 16-byte

@@ -35,15 +35,6 @@ struct HistArgs {
   float* part_e;              // [grid][MAXO][2]
 };
 
-// The bin rule of the definition (hist_affine and hist_speed: hist_common.h): each line is one correctly rounded fp32 operation.
-__host__ __device__ inline int hist_bin(float y, float lo, float inv_w, int nbins) {
-#pragma clang fp contract(off)
-  const float d = y - lo;
-  const float t = d * inv_w;
-  const int b = t < 0.f ? 0 : t >= (float)nbins ? nbins + 1 : 1 + (int)t;   // selects, not branches
-  return t != t ? nbins + 2 : b;
-}
-
 __device__ __forceinline__ double shfl_xor_d(double v, int m) {
   return __longlong_as_double(__shfl_xor(__double_as_longlong(v), m, 64));
 }

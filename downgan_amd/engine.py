@@ -1236,7 +1236,7 @@ class TrainEngine:
         self.ops.l1(fake, fine, self._sc("l1_sum"), grad=self.dfake, grad_scale=hp.content_lambda / (self.n_real_elems * self.world),
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
-    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None):
+    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1252,7 +1252,9 @@ class TrainEngine:
         ``maps``: a paired ``gridstats.GridStats`` that receives (fine[:n], fake[:n]) in one call: the per-gridpoint statistics
         of both series and of their difference.
         ``fss``: a ``fss.FractionsSkill`` that likewise receives (fine[:n], fake[:n]) in one call: the fractions skill score's
-        exact sums of the pair."""
+        exact sums of the pair.
+        ``joint``: a ``joint.ValueJoint`` that likewise receives (fine[:n], fake[:n]) in one call: the wind roses and the
+        real-vs-generated densities of the pair."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1271,6 +1273,8 @@ class TrainEngine:
             maps.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if fss is not None:
             fss.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if joint is not None:
+            joint.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

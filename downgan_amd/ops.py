@@ -882,6 +882,29 @@ class HipOps:
         check(self.lib.dg_hist(C.byref(f), C.byref(spec), _ptr(ws), _ptr(counts), _ptr(moments), _ptr(extrema), self._stream()),
               "dg_hist")
 
+    # ------------------------------------------------------------------ joint histograms (csrc/joint.hip)
+    def hist2d_ws_bytes(self, fa, fb, spec):
+        """Workspace bytes of one dg_hist2d call over the descriptors ``fa`` (and ``fb``, or None) with the _lib.Hist2dSpec
+        ``spec`` (0: invalid)."""
+        return int(self.lib.dg_hist2d_ws_bytes(C.byref(fa), C.byref(fb) if fb is not None else None, C.byref(spec)))
+
+    def hist2d(self, fa, fb, spec, counts):
+        """Accumulate the joint histograms of the fields of ``fa`` (eof_fields; ``fb``: the second series, or None) under
+        ``spec`` (_lib.Hist2dSpec): counts int64, the [nbx + 3, nby + 3] tables of the pairs concatenated in pair order, +=.
+        The workspace is cached on this object."""
+        n = sum((spec.ax[p][0].nbins + 3) * (spec.ax[p][1].nbins + 3) for p in range(spec.npairs))
+        assert counts.dtype == torch.int64 and counts.is_contiguous() and counts.numel() == n and counts.is_cuda, \
+            (counts.dtype, counts.shape, n)
+        assert fb is None or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.hist2d_ws_bytes(fa, fb, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, spec.npairs)
+        ws = getattr(self, "_hist2d_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._hist2d_ws = ws = None
+            self._hist2d_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_hist2d(C.byref(fa), C.byref(fb) if fb is not None else None, C.byref(spec), _ptr(ws), _ptr(counts),
+                                 self._stream()), "dg_hist2d")
+
     # ------------------------------------------------------------------ per-gridpoint statistics (csrc/gridstats.hip)
     def gridstats_ws_bytes(self, f, paired, spec):
         """Workspace bytes of one dg_gridstats call over the descriptor ``f`` (one series, or with ``paired`` two) with the

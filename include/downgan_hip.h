@@ -639,6 +639,62 @@ int dg_fss(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const d
 int dg_fss_host(const dg_fss_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* sums, int64_t* rates);
 int64_t dg_fss_bound(int H, int W, int win);
 
+/* ---- Joint histograms (csrc/joint.hip) -------------------------------------------------------------------------------------
+ * Wind roses and real-vs-generated densities: 2-D histograms over one or two series of fields of equal T, C, P, each read in
+ * place through the EOF descriptor (NCHW fp32 / bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC
+ * output; a and b may differ in layout and dtype).  Series a is the real fields (or the only series), b the generated ones.
+ * The output values are those of the value histograms (the same code, csrc/hist_common.h), one transform for both series,
+ * every fp32 operation rounded once, never contracted:
+ *   y_c = (x_c * scale[c]) + offset[c]
+ *   s   = sqrt(y_u * y_u + y_v * y_v)                       speed_u >= 0: the speed of the pair (u, v)
+ * An AXIS is (src: 0 = a, 1 = b; chan; nbins; lo; inv_w).  chan 0 .. C-1 is a component, chan = C the speed, chan = C + 1 the
+ * direction.  Component and speed axes use the bin rule of the value histograms (hist_bin): index 0 underflow, 1 .. nbins
+ * interior, nbins + 1 overflow, nbins + 2 NaN.  A DIRECTION axis has nbins = nsec sectors in the meteorological convention
+ * (where the wind comes from, clockwise from north, sector 0 centred on north); nsec is a multiple of 4 in 4 .. 72, shared by
+ * every direction axis of the spec, K = nsec / 4, tan_k[k] = fp32(tan(k pi / (4 K))) for k = 1 .. K-1 rounded once from
+ * float64 (tan_k[0] is not read), calm is finite and >= 0.  The direction rule, in this order (no atan2: it is not correctly
+ * rounded, so it cannot be part of an exact contract):
+ *   1. y_u or y_v NaN                       -> index nsec + 2
+ *   2. not (s > calm)                       -> index 0 (calm); index nsec + 1 is never used
+ *   3. x = -y_u, y = -y_v, ax = |x|, ay = |y|, swap = ax > ay
+ *   4. m = swap ? ay : ax,  M = swap ? ax : ay
+ *   5. j = #{k in 1 .. K-1 : m >= fp32(M * tan_k[k])}       one rounded multiply per k
+ *   6. q = swap ? 2K - 1 - j : j
+ *   7. half sector h = q          if x >= 0 && y > 0
+ *                      4K - 1 - q if x > 0 && y <= 0
+ *                      4K + q     if x <= 0 && y < 0
+ *                      8K - 1 - q if x < 0 && y >= 0
+ *   8. sector = ((h + 1) >> 1) mod nsec, index = 1 + sector
+ * A PAIR is two axes (X, Y); its table is int64 [nbx + 3][nby + 3], row-major, X first, at most DG_HIST2D_MAX_CELLS cells; a
+ * spec holds 1 .. DG_HIST2D_MAX_PAIRS pairs and counts holds their tables concatenated in pair order.  Since every axis uses the
+ * 1-D rule, the marginals of a table equal the dg_hist counts of the same axis exactly.
+ * Consecutive pairs are packed into groups whose uint32 tables together fit the LDS budget of one workgroup; one group is one
+ * launch that reads the input once: every workgroup keeps the group's tables in LDS (ds_add_u32) and adds the non-zero cells
+ * to counts with 64-bit integer atomics.  Nothing is summed in floating point: the counts are exact for any T * P and two calls
+ * on the same data are bit-identical.
+ *
+ * dg_hist2d_ws_bytes: workspace bytes of one call; 0 for an invalid call, else a small non-zero value (no workspace is needed).
+ * dg_hist2d: ACCUMULATES into counts (the caller zeroes them).  b NULL unless an axis has src 1.  Rejected before any launch
+ *   (DG_ERR_BAD_SHAPE; DG_ERR_BAD_DTYPE for a dtype other than fp32 / bf16): a NULL pointer, npairs outside 1 ..
+ *   DG_HIST2D_MAX_PAIRS, a table above the cell cap, nbins < 1, a non-finite lo or inv_w or inv_w <= 0, a chan that does not
+ *   exist, a speed or direction axis without a speed pair, a direction axis whose nbins != nsec, a bad nsec, a negative or
+ *   non-finite calm, src 1 with b NULL, series that differ in T, C or P.
+ * dg_hist2d_host_bins: host-side, the same transform and rules for xa, xb fp32 [C][n] (planar; xb may be NULL when no axis has
+ *   src 1): bins int32 [npairs][2][n], the X and the Y index of every point under every pair. */
+#define DG_HIST2D_MAX_PAIRS 8
+#define DG_HIST2D_MAX_CELLS 16384
+#define DG_HIST2D_MAX_SECTORS 72
+typedef struct dg_hist2d_axis { int src, chan, nbins; float lo, inv_w; } dg_hist2d_axis;
+typedef struct dg_hist2d_spec {
+  int npairs, speed_u, speed_v, nsec;
+  float calm, tan_k[DG_HIST2D_MAX_SECTORS / 4];
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];
+  dg_hist2d_axis ax[DG_HIST2D_MAX_PAIRS][2];
+} dg_hist2d_spec;
+size_t dg_hist2d_ws_bytes(const dg_eof_fields* a, const dg_eof_fields* b, const dg_hist2d_spec* s);
+int dg_hist2d(const dg_eof_fields* a, const dg_eof_fields* b, const dg_hist2d_spec* s, void* ws, int64_t* counts, void* stream);
+int dg_hist2d_host_bins(const dg_hist2d_spec* s, const float* xa, const float* xb, int C, int64_t n, int32_t* bins);
+
 #ifdef __cplusplus
 }
 #endif
