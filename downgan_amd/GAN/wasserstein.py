@@ -147,13 +147,15 @@ class WassersteinGAN:
         o.gp_finish(e.ss, B, B * e.world, e.hp.gp_lambda, 0.0, e.coef, e._sc("gp_ret"))
         return float(e._sc("gp_ret").item())
 
-    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None):
+    def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
+                                  coherence=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
         ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
         mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
-        ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair."""
+        ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair;
+        ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -165,10 +167,12 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint)
+            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
+                                  coherence=coherence)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint)
+        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
+                              coherence=coherence)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -202,6 +206,11 @@ class WassersteinGAN:
     log_joint = False
     joint_spec = None
     joint_results = None         # the last epoch's {"train" / "test": joint.Joint} when logged
+    # opt-in: cross spectra of the same (real, generated) pairs -- per-scale coherence, relative error spectrum and the effective
+    # resolution (the last wavenumber down to which the coherence stays >= coherence_threshold), reported per epoch in
+    # summary["coherence"]
+    log_coherence = False
+    coherence_threshold = 0.5
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -238,9 +247,14 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return ValueJoint(spec, device=dev)
 
+    def _coherence_acc(self, fine):
+        from ..spectra import CrossSpectrum
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return CrossSpectrum(self.G.n_predictands, fine.shape[-1], device=dev)
+
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -268,7 +282,24 @@ class WassersteinGAN:
             if part not in j:
                 j[part] = self._joint_acc()
             kw["joint"] = j[part]
+        if self.log_coherence:
+            c = acc.setdefault("coherence", {})
+            if part not in c:
+                c[part] = self._coherence_acc(fine)
+            kw["coherence"] = c[part]
         return kw
+
+    def _coherence_summary(self, acc):
+        """{"real", "fake", "co": [C][K] mean spectra of the real and generated fields and their co-spectrum, "coherence",
+        "rel_error": [C][K], "k_eff", "wavelength_px": [C] effective resolution at ``coherence_threshold``, "fields": count} of
+        one part's accumulator, summed over the data-parallel ranks first."""
+        from ..spectra import coherence, effective_resolution, relative_error_spectrum, wavelength_px
+        s = acc.reduce_(self.dist).mean().cpu().numpy()
+        coh = coherence(s)
+        k_eff = effective_resolution(coh, self.coherence_threshold)
+        return {"real": s[:, 0].tolist(), "fake": s[:, 1].tolist(), "co": s[:, 2].tolist(), "coherence": coh.tolist(),
+                "rel_error": relative_error_spectrum(s).tolist(), "k_eff": [int(k) for k in k_eff],
+                "wavelength_px": [float(w) for w in wavelength_px(k_eff, acc.N)], "fields": acc.count}
 
     def _joint_summary(self, part, acc):
         """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
@@ -323,7 +354,7 @@ class WassersteinGAN:
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
         log, train_metrics, test_metrics = [], [], []
-        acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" / "joint" -> {"train" / "test": accumulators}
+        acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" / "joint" / "coherence" -> {"train" / "test": accumulators}
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
@@ -353,7 +384,8 @@ class WassersteinGAN:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
-        if self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint:
+        if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
+                or self.log_coherence):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -371,6 +403,8 @@ class WassersteinGAN:
             if self.log_joint:
                 self.joint_results = {}
                 summary["joint"] = {k: self._joint_summary(k, v) for k, v in acc.get("joint", {}).items()}
+            if self.log_coherence:
+                summary["coherence"] = {k: self._coherence_summary(v) for k, v in acc.get("coherence", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

@@ -11,6 +11,17 @@
 // Ring k holds the frequencies (u, v) (signed, |u|, |v| <= N/2) with (2k-1)^2 <= 4 (u^2 + v^2) < (2k+1)^2, evaluated in integers:
 // r^2 in [k^2 - k + 1, k^2 + k] (k = 0: r^2 = 0).  Rings k > N/2 (the corners) are dropped.  No float atomics anywhere: two
 // calls on the same data are bit-identical.
+//
+// Cross spectra (include/downgan_hip.h "Cross spectra") of paired fields a, b: ring means of |A|^2 / N^2, |B|^2 / N^2 and
+// Re(A conj B) / N^2 over the same rings.
+//   rapsd_row_kernel       unchanged, once per side, into two half-spectrum buffers (each side has its own layout and dtype)
+//   cross_col_kernel       per slice of lines u of a pair: FFT of side a's lines (kept in a third LDS buffer), FFT of side b's
+//                          lines, the three weighted products per point, ring sums of each plane in fp64; the slices, the loop
+//                          order and the power expression are those of rapsd_col_kernel, so planes 0 and 1 equal dg_rapsd of a
+//                          and of b bit for bit.  LDS: 3 x 16 KB line buffers + 16 KB twiddles = 64 KB per workgroup, so two
+//                          workgroups (8 waves) share a CU's 160 KB; rapsd_col_kernel's 48 KB would admit three.
+//   cross_field_kernel     slices summed in order, divided by the ring counts -> per-field [3][K]
+//   cross_sum_kernel       sum[c][plane][k] over t, in t order
 #include "dg_internal.h"
 
 namespace {
@@ -242,6 +253,131 @@ __global__ __launch_bounds__(256) void rapsd_sum_kernel(const double* pf, int Tn
   sum[idx] = s;
 }
 
+struct CrossCol {
+  const float2* spec_a;
+  const float2* spec_b;
+  const float2* tw;
+  int N, logN, S, L;          // the slices of rapsd_ws
+  double* part;               // [F][S][3][N/2 + 1]
+};
+
+// nl whole lines of one half spectrum (contiguous) into an LDS buffer, the rest of the buffer zero
+__device__ __forceinline__ void cross_load_lines(float2* dst, const float2* lines, int nl, int logN) {
+  const float4* src4 = reinterpret_cast<const float4*>(lines);
+  for (int idx = threadIdx.x; idx < RAPSD_PTS / 2; idx += 256) {
+    const float4 v = (2 * idx >> logN) < nl ? src4[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+    dst[2 * idx] = make_float2(v.x, v.y);
+    dst[2 * idx + 1] = make_float2(v.z, v.w);
+  }
+}
+
+// LDS: buf[0], buf[1] are fft_lds's pair, buf[2] keeps side a's transformed lines while side b's run through the pair; after
+// the products, planes 0 and 1 lie in the pair's free buffer and plane 2 over buf[2].  3 x 16 KB + 16 KB twiddles = 64 KB.
+__global__ __launch_bounds__(256) void cross_col_kernel(CrossCol a) {
+  __shared__ float2 buf[3][RAPSD_PTS];
+  __shared__ float2 tw[DG_RAPSD_MAX_N];
+  constexpr int PT = RAPSD_PTS / 256;                           // points per thread
+  const int N = a.N, logN = a.logN, nfft = RAPSD_PTS >> logN, K = N / 2 + 1;
+  const long long f = blockIdx.x / a.S;
+  const int s = blockIdx.x % a.S;
+  const int u_end = min(K, (s + 1) * a.L);
+  const float inv = 1.f / ((float)N * (float)N);              // a power of two: exact
+  for (int m = threadIdx.x; m < N; m += 256) tw[m] = a.tw[m];
+  double acc[3][RAPSD_KQ];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int q = 0; q < RAPSD_KQ; ++q) acc[p][q] = 0.0;
+  for (int u0 = s * a.L; u0 < u_end; u0 += nfft) {
+    const int nl = min(nfft, u_end - u0);
+    const long long line0 = (f * K + u0) * N;
+    cross_load_lines(buf[0], a.spec_a + line0, nl, logN);
+    __syncthreads();
+    int r = fft_lds(buf, tw, N, logN);
+    for (int idx = threadIdx.x; idx < RAPSD_PTS; idx += 256) buf[2][idx] = buf[r][idx];
+    __syncthreads();                                            // side b's lines overwrite buf[0]
+    cross_load_lines(buf[0], a.spec_b + line0, nl, logN);
+    __syncthreads();
+    r = fft_lds(buf, tw, N, logN);
+    float* pw = reinterpret_cast<float*>(buf[r ^ 1]);           // planes 0 and 1
+    float co[PT];
+#pragma unroll
+    for (int i = 0; i < PT; ++i) {
+      const int idx = threadIdx.x + 256 * i;
+      const int u = u0 + (idx >> logN);
+      const float w = u == 0 || u == N / 2 ? 1.f : 2.f;
+      const float2 A = buf[2][idx], B = buf[r][idx];
+      pw[idx] = fmaf(A.x, A.x, A.y * A.y) * inv * w;
+      pw[RAPSD_PTS + idx] = fmaf(B.x, B.x, B.y * B.y) * inv * w;
+      co[i] = fmaf(A.x, B.x, A.y * B.y) * inv * w;
+    }
+    __syncthreads();                                            // every A is read: plane 2 goes over buf[2]
+    float* pc = reinterpret_cast<float*>(buf[2]);
+#pragma unroll
+    for (int i = 0; i < PT; ++i) pc[threadIdx.x + 256 * i] = co[i];
+    __syncthreads();
+    for (int j = 0; j < nl; ++j) {
+      const float* pa = pw + (j << logN);
+      const float* pb = pa + RAPSD_PTS;
+      const float* pl = pc + (j << logN);
+#pragma unroll
+      for (int q = 0; q < RAPSD_KQ; ++q) {
+        const int k = threadIdx.x + 256 * q;
+        if (k >= K) continue;
+        int vmin, vmax;
+        ring_span(u0 + j, k, N, vmin, vmax);
+        double sa = 0.0, sb = 0.0, sc = 0.0;
+        for (int v = vmin; v <= vmax; ++v) {
+          sa += (double)pa[v];
+          sb += (double)pb[v];
+          sc += (double)pl[v];
+          if (v != 0 && v != N / 2) {
+            sa += (double)pa[N - v];
+            sb += (double)pb[N - v];
+            sc += (double)pl[N - v];
+          }
+        }
+        acc[0][q] += sa;
+        acc[1][q] += sb;
+        acc[2][q] += sc;
+      }
+    }
+    __syncthreads();                                            // the next batch overwrites buf
+  }
+  double* out = a.part + (f * a.S + s) * 3 * K;
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int q = 0; q < RAPSD_KQ; ++q) {
+      const int k = threadIdx.x + 256 * q;
+      if (k < K) out[p * K + k] = acc[p][q];
+    }
+}
+
+// one thread per (field, plane, ring): the slices in order
+__global__ __launch_bounds__(256) void cross_field_kernel(const double* part, const double* cnt, long long F, int S, int K,
+                                                          double* pf, double* per_field) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= F * 3 * K) return;
+  const long long f = idx / (3 * K);
+  const int pk = (int)(idx % (3 * K));                          // plane * K + ring
+  const double* q = part + f * S * 3 * K + pk;
+  double s = 0.0;
+  for (int i = 0; i < S; ++i) s += q[(long long)i * 3 * K];
+  s /= cnt[pk % K];
+  pf[idx] = s;
+  if (per_field) per_field[idx] = s;
+}
+
+// one thread per (channel, plane, ring): the fields in t order
+__global__ __launch_bounds__(256) void cross_sum_kernel(const double* pf, int Tn, int C, int K, double* sum) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= C * 3 * K) return;
+  double s = 0.0;
+  for (int t = 0; t < Tn; ++t) s += pf[(long long)t * C * 3 * K + idx];
+  sum[idx] = s;
+}
+
 // workspace: twiddles, counts, spec, slice partials, per-field spectra (each 256-byte aligned)
 struct RapsdWs {
   size_t tw, cnt, spec, part, pf, bytes;
@@ -269,6 +405,42 @@ RapsdWs rapsd_ws(long long F, int N) {
   return w;
 }
 
+// cross spectra: twiddles, counts, both sides' spec, slice partials [F][S][3][K], per-field [F][3][K]; S and L as rapsd_ws
+struct CrossWs {
+  size_t tw, cnt, spec_a, spec_b, part, pf, bytes;
+  int S, L;
+};
+
+CrossWs cross_ws(long long F, int N) {
+  const RapsdWs r = rapsd_ws(F, N);
+  const int K = N / 2 + 1;
+  CrossWs w;
+  w.S = r.S;
+  w.L = r.L;
+  w.tw = 0;
+  w.cnt = w.tw + align256((size_t)N * 8);
+  w.spec_a = w.cnt + align256((size_t)K * 8);
+  w.spec_b = w.spec_a + align256((size_t)F * K * N * 8);
+  w.part = w.spec_b + align256((size_t)F * K * N * 8);
+  w.pf = w.part + align256((size_t)F * w.S * 3 * K * 8);
+  w.bytes = w.pf + align256((size_t)F * 3 * K * 8);
+  return w;
+}
+
+bool rapsd_fields_ok(const dg_eof_fields* x, int N) {
+  return x && x->base && x->T >= 1 && x->C >= 1 && x->C <= DG_EOF_MAX_C && x->P == N * N && x->ld_t >= 0 && x->ld_c >= 0 &&
+         x->ld_p >= 0;
+}
+
+void launch_row(const dg_eof_fields* x, int N, long long npairs, long long row_blocks, const float2* tw, float2* spec,
+                hipStream_t st) {
+  RapsdRow r;
+  r.base = x->base; r.ld_t = x->ld_t; r.ld_c = x->ld_c; r.ld_p = x->ld_p;
+  r.C = x->C; r.N = N; r.logN = __builtin_ctz(N); r.npairs = npairs; r.tw = tw; r.spec = spec;
+  if (x->dtype == DG_F32) hipLaunchKernelGGL(rapsd_row_kernel<float>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
+  else hipLaunchKernelGGL(rapsd_row_kernel<bf16_t>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
+}
+
 }  // namespace
 
 extern "C" size_t dg_rapsd_ws_bytes(int T, int C, int N) {
@@ -283,9 +455,7 @@ extern "C" int dg_rapsd_ring_counts(int N, int64_t* counts) {
 }
 
 extern "C" int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_field, double* sum, void* stream) {
-  if (!x || !x->base || !ws || !rapsd_n_ok(N) || x->T < 1 || x->C < 1 || x->C > DG_EOF_MAX_C || x->P != N * N || x->ld_t < 0 ||
-      x->ld_c < 0 || x->ld_p < 0)
-    return DG_ERR_BAD_SHAPE;
+  if (!ws || !rapsd_n_ok(N) || !rapsd_fields_ok(x, N)) return DG_ERR_BAD_SHAPE;
   if (x->dtype != DG_F32 && x->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
   const long long F = (long long)x->T * x->C;
   const int K = N / 2 + 1, logN = __builtin_ctz(N), nfft = RAPSD_PTS / N;
@@ -302,11 +472,7 @@ extern "C" int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_fie
   double* pf = reinterpret_cast<double*>(b + w.pf);
   hipLaunchKernelGGL(rapsd_twiddle_kernel, dim3((N + 255) / 256), dim3(256), 0, st, tw, N);
   hipLaunchKernelGGL(rapsd_count_kernel, dim3((K + 255) / 256), dim3(256), 0, st, cnt, N);
-  RapsdRow r;
-  r.base = x->base; r.ld_t = x->ld_t; r.ld_c = x->ld_c; r.ld_p = x->ld_p;
-  r.C = x->C; r.N = N; r.logN = logN; r.npairs = npairs; r.tw = tw; r.spec = spec;
-  if (x->dtype == DG_F32) hipLaunchKernelGGL(rapsd_row_kernel<float>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
-  else hipLaunchKernelGGL(rapsd_row_kernel<bf16_t>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
+  launch_row(x, N, npairs, row_blocks, tw, spec, st);
   RapsdCol c;
   c.spec = spec; c.tw = tw; c.N = N; c.logN = logN; c.S = w.S; c.L = w.L; c.part = part;
   hipLaunchKernelGGL(rapsd_col_kernel, dim3((unsigned)col_blocks), dim3(256), 0, st, c);
@@ -315,5 +481,44 @@ extern "C" int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_fie
   if (sum)
     hipLaunchKernelGGL(rapsd_sum_kernel, dim3((unsigned)((x->C * K + 255) / 256)), dim3(256), 0, st, (const double*)pf, x->T, x->C,
                        K, sum);
+  return dg_check_launch();
+}
+
+extern "C" size_t dg_cross_rapsd_ws_bytes(int T, int C, int N) {
+  if (T < 1 || C < 1 || C > DG_EOF_MAX_C || !rapsd_n_ok(N)) return 0;
+  return cross_ws((long long)T * C, N).bytes;
+}
+
+extern "C" int dg_cross_rapsd(const dg_eof_fields* a, const dg_eof_fields* b, int N, void* ws, double* per_field, double* sum,
+                              void* stream) {
+  if (!ws || !rapsd_n_ok(N) || !rapsd_fields_ok(a, N) || !rapsd_fields_ok(b, N) || a->T != b->T || a->C != b->C)
+    return DG_ERR_BAD_SHAPE;
+  if ((a->dtype != DG_F32 && a->dtype != DG_BF16) || (b->dtype != DG_F32 && b->dtype != DG_BF16)) return DG_ERR_BAD_DTYPE;
+  const long long F = (long long)a->T * a->C;
+  const int K = N / 2 + 1, logN = __builtin_ctz(N), nfft = RAPSD_PTS / N;
+  const CrossWs w = cross_ws(F, N);
+  const long long npairs = F * (N / 2);
+  const long long row_blocks = (npairs + nfft - 1) / nfft, col_blocks = F * w.S;
+  if (row_blocks > 0x7fffffffLL || col_blocks > 0x7fffffffLL || F * 3 * K > 0x7fffffffLL * 256LL) return DG_ERR_BAD_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(ws);
+  float2* tw = reinterpret_cast<float2*>(base + w.tw);
+  double* cnt = reinterpret_cast<double*>(base + w.cnt);
+  float2* spec_a = reinterpret_cast<float2*>(base + w.spec_a);
+  float2* spec_b = reinterpret_cast<float2*>(base + w.spec_b);
+  double* part = reinterpret_cast<double*>(base + w.part);
+  double* pf = reinterpret_cast<double*>(base + w.pf);
+  hipLaunchKernelGGL(rapsd_twiddle_kernel, dim3((N + 255) / 256), dim3(256), 0, st, tw, N);
+  hipLaunchKernelGGL(rapsd_count_kernel, dim3((K + 255) / 256), dim3(256), 0, st, cnt, N);
+  launch_row(a, N, npairs, row_blocks, tw, spec_a, st);
+  launch_row(b, N, npairs, row_blocks, tw, spec_b, st);
+  CrossCol c;
+  c.spec_a = spec_a; c.spec_b = spec_b; c.tw = tw; c.N = N; c.logN = logN; c.S = w.S; c.L = w.L; c.part = part;
+  hipLaunchKernelGGL(cross_col_kernel, dim3((unsigned)col_blocks), dim3(256), 0, st, c);
+  hipLaunchKernelGGL(cross_field_kernel, dim3((unsigned)((F * 3 * K + 255) / 256)), dim3(256), 0, st, (const double*)part,
+                     (const double*)cnt, F, w.S, K, pf, per_field);
+  if (sum)
+    hipLaunchKernelGGL(cross_sum_kernel, dim3((unsigned)((a->C * 3 * K + 255) / 256)), dim3(256), 0, st, (const double*)pf, a->T,
+                       a->C, K, sum);
   return dg_check_launch();
 }

@@ -1236,7 +1236,8 @@ class TrainEngine:
         self.ops.l1(fake, fine, self._sc("l1_sum"), grad=self.dfake, grad_scale=hp.content_lambda / (self.n_real_elems * self.world),
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
-    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None):
+    def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None,
+                     coherence=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1254,7 +1255,9 @@ class TrainEngine:
         ``fss``: a ``fss.FractionsSkill`` that likewise receives (fine[:n], fake[:n]) in one call: the fractions skill score's
         exact sums of the pair.
         ``joint``: a ``joint.ValueJoint`` that likewise receives (fine[:n], fake[:n]) in one call: the wind roses and the
-        real-vs-generated densities of the pair."""
+        real-vs-generated densities of the pair.
+        ``coherence``: a ``spectra.CrossSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the cross spectra
+        of the pair (per-scale coherence, error spectrum, effective resolution)."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1266,6 +1269,8 @@ class TrainEngine:
         if spectra is not None:
             spectra[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
             spectra[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if coherence is not None:
+            coherence.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if distributions is not None:
             distributions[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
             distributions[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)

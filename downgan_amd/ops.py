@@ -860,6 +860,28 @@ class HipOps:
             self._rapsd_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
         check(self.lib.dg_rapsd(C.byref(f), int(N), _ptr(ws), _ptr(per_field), _ptr(sum), self._stream()), "dg_rapsd")
 
+    def cross_rapsd_ws_bytes(self, T, Cn, N):
+        """Workspace bytes of one dg_cross_rapsd call over T pairs of Cn channels, N x N (0: not a valid shape)."""
+        return int(self.lib.dg_cross_rapsd_ws_bytes(int(T), int(Cn), int(N)))
+
+    def cross_rapsd(self, fa, fb, N, per_field=None, sum=None):
+        """Ring-averaged cross spectra of the paired N x N fields of the descriptors ``fa``, ``fb`` (eof_fields, P = N*N, the same
+        T and C, layouts and dtypes independent): per_field [T, C, 3, N/2+1] and / or sum [C, 3, N/2+1] (sum over the T pairs,
+        in order), planes |A|^2, |B|^2, Re(A conj B); fp64 contiguous, either may be None.  The workspace is ``rapsd``'s cached
+        buffer (the two never run at once on the stream), grown to the largest call of either."""
+        K = N // 2 + 1
+        assert (fa.T, fa.C, fa.P) == (fb.T, fb.C, fb.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        for out, n in ((per_field, fa.T * fa.C * 3 * K), (sum, fa.C * 3 * K)):
+            assert out is None or (out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n and out.is_cuda)
+        nb = self.cross_rapsd_ws_bytes(fa.T, fa.C, N)
+        assert nb > 0, (fa.T, fa.C, N)
+        ws = getattr(self, "_rapsd_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._rapsd_ws = ws = None
+            self._rapsd_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_cross_rapsd(C.byref(fa), C.byref(fb), int(N), _ptr(ws), _ptr(per_field), _ptr(sum), self._stream()),
+              "dg_cross_rapsd")
+
     # ------------------------------------------------------------------ value histograms (csrc/histogram.hip)
     def hist_ws_bytes(self, f, spec):
         """Workspace bytes of one dg_hist call over the descriptor ``f`` with the _lib.HistSpec ``spec`` (0: invalid)."""

@@ -11,6 +11,15 @@ input lacks?  For one square field x (N x N, N a power of two, 16 <= N <= 2048):
 (fp32 or bf16).  ``RadialSpectrum`` accumulates the spectra of many batches on the device (and over data-parallel ranks);
 the trainer's opt-in hook (``WassersteinGAN.log_spectra``) keeps one for the real and one for the generated fields.  Every
 reduction runs in a fixed order: two calls on the same data are bit-identical.
+
+The RAPSD is phase-blind: a generator can match it perfectly while every small-scale phase is unrelated to the truth.
+``cross_rapsd`` takes the PAIRED fields a, b (A = fft2(a), B = fft2(b)) and returns three ring means per wavenumber,
+
+    plane 0 = |A|^2 / N^2,  plane 1 = |B|^2 / N^2,  plane 2 = Re(A conj B) / N^2   (planes 0, 1: bit-equal to ``rapsd``)
+
+from which follow the ``coherence`` s2 / sqrt(s0 s1), the ``error_spectrum`` s0 + s1 - 2 s2 (the ring power of a - b) and the
+``effective_resolution``: the last wavenumber down to which the coherence stays above a threshold, i.e. the scale below which
+the generated field is only plausible texture.  ``CrossSpectrum`` is the accumulator (``WassersteinGAN.log_coherence``).
 """
 from __future__ import annotations
 
@@ -144,6 +153,175 @@ def log_spectral_distance(p_ref, p, kmin=1):
     d = 10.0 * np.log10(b[..., kmin:] / a[..., kmin:])
     out = np.sqrt(np.mean(d * d, axis=-1))
     return float(out) if out.ndim == 0 else out
+
+
+def _pair(a, b, channels, nhwc, nhwc_b):
+    """Validate both sides and their agreement without touching a device -> ((a, nhwc_a), (b, nhwc_b), C, T, N)."""
+    a, na, Ca, Ta, Na = _fields(a, channels, nhwc)
+    b, nb, Cb, Tb, Nb = _fields(b, channels, nhwc if nhwc_b is None else nhwc_b)
+    if (Ta, Ca, Na) != (Tb, Cb, Nb):
+        raise ValueError(f"cross spectra need paired fields: a has T, C, N = {Ta}, {Ca}, {Na} and b has {Tb}, {Cb}, {Nb}")
+    if a.device != b.device:
+        raise ValueError(f"cross spectra need both sides on one device (got {a.device} and {b.device})")
+    return (a, na), (b, nb), Ca, Ta, Na
+
+
+def _cross_chunk(o, T, Cn, N):
+    """Pairs per dg_cross_rapsd call: the fewest calls whose workspace stays within WS_CAP bytes (at least one pair a call),
+    then the T pairs spread evenly over them (32 go as 16 + 16, not 31 + 1)."""
+    tc = min(T, max(1, WS_CAP // max(1, o.cross_rapsd_ws_bytes(1, Cn, N))))
+    while tc > 1 and o.cross_rapsd_ws_bytes(tc, Cn, N) > WS_CAP:
+        tc -= 1
+    calls = -(-T // tc)
+    return -(-T // calls)
+
+
+def _cross_sum_into(o, a, b, Cn, T, N, total):
+    """total [C, 3, K] fp64 (device) += sum over the T pairs of their cross spectra; chunk sums added in order."""
+    (a, na), (b, nb) = a, b
+    tc = _cross_chunk(o, T, Cn, N)
+    part = torch.empty_like(total)
+    for t0 in range(0, T, tc):
+        xa, fa = _descriptor(o, a[t0:t0 + tc], na, Cn)
+        xb, fb = _descriptor(o, b[t0:t0 + tc], nb, Cn)
+        o.cross_rapsd(fa, fb, N, sum=part)
+        total += part
+
+
+def cross_rapsd(a, b, channels=None, nhwc=False, nhwc_b=None, per_field=False, ops=None):
+    """Radially averaged cross spectra of a series of paired square fields on the GPU.
+
+    a, b: as ``rapsd``'s x, with the same T, C and N; the layouts (``nhwc`` for a, ``nhwc_b`` for b, default: as a) and the
+    dtypes are independent (the trainer's real side is the staged NHWC store, its generated side the padded bf16 output).
+    Returns float64 [C, 3, N/2 + 1], the mean over T of the planes |A|^2 / N^2, |B|^2 / N^2 and Re(A conj B) / N^2, or
+    [T, C, 3, N/2 + 1] with ``per_field``.  Per library call planes 0 and 1 equal ``dg_rapsd`` of
+    a and of b bit for bit, and so do they here whenever ``rapsd`` splits the series into the same calls (always when both fit
+    one call); where they split differently the slice sums run in another order and the two agree to fp64 rounding.
+    Cross-channel coherence (u against v of one field) needs nothing extra: ``cross_rapsd(x[:, :1], x[:, 1:2])``."""
+    sa, sb, Cn, T, N = _pair(a, b, channels, nhwc, nhwc_b)
+    dev = sa[0].device
+    o = ops if ops is not None else _default_ops(dev)
+    K = N // 2 + 1
+    if per_field:
+        out = torch.empty(T, Cn, 3, K, dtype=torch.float64, device=dev)
+        tc = _cross_chunk(o, T, Cn, N)
+        for t0 in range(0, T, tc):
+            xa, fa = _descriptor(o, sa[0][t0:t0 + tc], sa[1], Cn)
+            xb, fb = _descriptor(o, sb[0][t0:t0 + tc], sb[1], Cn)
+            o.cross_rapsd(fa, fb, N, per_field=out[t0:t0 + tc])
+        return out
+    total = torch.zeros(Cn, 3, K, dtype=torch.float64, device=dev)
+    _cross_sum_into(o, sa, sb, Cn, T, N, total)
+    return total / T
+
+
+def _host(v):
+    return v.detach().cpu().double().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+
+
+def _planes(s):
+    s = _host(s)
+    if s.ndim < 2 or s.shape[-2] != 3:
+        raise ValueError(f"cross spectra are [..., 3, K] (got shape {s.shape})")
+    return s[..., 0, :], s[..., 1, :], s[..., 2, :]
+
+
+def coherence(s):
+    """s2 / sqrt(s0 s1) per wavenumber: cross spectra [..., 3, K] -> numpy float64 [..., K]; NaN where the denominator is 0."""
+    s0, s1, s2 = _planes(s)
+    den = np.sqrt(s0 * s1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(den == 0, np.nan, s2 / den)
+
+
+def error_spectrum(s):
+    """s0 + s1 - 2 s2, the ring power of a - b: [..., 3, K] -> numpy float64 [..., K]."""
+    s0, s1, s2 = _planes(s)
+    return s0 + s1 - 2.0 * s2
+
+
+def relative_error_spectrum(s):
+    """error_spectrum / s0 (the error's power relative to side a's, 2 for unrelated fields of equal power): [..., K]."""
+    s0, _, _ = _planes(s)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return error_spectrum(s) / s0
+
+
+def effective_resolution(coh, threshold=0.5):
+    """The largest k in 1 .. N/2 with coh[..., j] >= threshold for every 1 <= j <= k (0 when ring 1 fails; a NaN ring fails;
+    ring 0, the mean, is ignored): coherence [..., K] -> numpy int64 [...] ([K] -> an int)."""
+    c = _host(coh)
+    if c.ndim < 1 or c.shape[-1] < 2:
+        raise ValueError(f"effective_resolution: coherence is [..., K] with K >= 2 (got shape {c.shape})")
+    with np.errstate(invalid="ignore"):
+        ok = c[..., 1:] >= threshold                          # NaN compares false
+    k = np.logical_and.accumulate(ok, axis=-1).sum(axis=-1).astype(np.int64)
+    return int(k) if k.ndim == 0 else k
+
+
+def wavelength_px(k_eff, N):
+    """N / k_eff, the wavelength in grid points of wavenumber k_eff; inf for k_eff = 0."""
+    k = np.asarray(k_eff, dtype=np.float64)
+    with np.errstate(divide="ignore"):
+        out = np.where(k == 0, np.inf, N / np.where(k == 0, 1.0, k))
+    return float(out) if out.ndim == 0 else out
+
+
+class CrossSpectrum:
+    """Running mean of the cross spectra of paired C-channel N x N fields: fp64 sums [C, 3, K] and the pair count stay on the
+    device (one buffer, so ``reduce_`` is one all-reduce under data parallelism)."""
+
+    def __init__(self, C, N, device="cuda:0", ops=None):
+        check_n(N)
+        if not 1 <= C <= C_MAX:
+            raise ValueError(f"cross spectra take 1 <= C <= {C_MAX} channels (got C = {C})")
+        self.C, self.N, self.K = int(C), int(N), N // 2 + 1
+        self.device = torch.device(device)
+        self._ops = ops
+        self._acc = torch.zeros(self.C * 3 * self.K + 1, dtype=torch.float64, device=self.device)
+
+    @property
+    def ops(self):
+        if self._ops is None:
+            self._ops = _default_ops(self.device)
+        return self._ops
+
+    @property
+    def sums(self):
+        return self._acc[:-1].view(self.C, 3, self.K)
+
+    @property
+    def count(self):
+        """Number of pairs (per channel) added so far."""
+        return int(round(float(self._acc[-1].item())))
+
+    def add(self, a, b, n_valid=None, nhwc=False, nhwc_b=None, channels=None):
+        """Add the cross spectra of the first ``n_valid`` (default: all) pairs of a batch (layouts as ``cross_rapsd``)."""
+        sa, sb, Cn, T, N = _pair(a, b, channels, nhwc, nhwc_b)
+        if (Cn, N) != (self.C, self.N):
+            raise ValueError(f"CrossSpectrum({self.C}, {self.N}) given {Cn} channels of {N} x {N}")
+        n = T if n_valid is None else int(n_valid)
+        if not 1 <= n <= T:
+            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        _cross_sum_into(self.ops, (sa[0][:n], sa[1]), (sb[0][:n], sb[1]), Cn, n, N, self.sums)
+        self._acc[-1] += n
+        return self
+
+    def mean(self):
+        """float64 [C, 3, K]: the mean cross spectra of every pair added (and, after ``reduce_``, of every rank)."""
+        if self.count == 0:
+            raise ValueError("CrossSpectrum.mean: no field was added")
+        return self.sums / self._acc[-1]
+
+    def coherence(self):
+        """numpy float64 [C, K]: the coherence of the mean cross spectra."""
+        return coherence(self.mean())
+
+    def reduce_(self, dist):
+        """Sum the sums and counts over the data-parallel ranks of ``dist`` (downgan_amd.dist.Dist), once, in place."""
+        if dist is not None and dist.world_size > 1:
+            dist.allreduce_sum_(self._acc)
+        return self
 
 
 class RadialSpectrum:

@@ -519,6 +519,28 @@ size_t dg_rapsd_ws_bytes(int T, int C, int N);
 int dg_rapsd(const dg_eof_fields* x, int N, void* ws, double* per_field, double* sum, void* stream);
 int dg_rapsd_ring_counts(int N, int64_t* counts);
 
+/* ---- Cross spectra (csrc/spectra.hip) ----------------------------------------------------------------------------------
+ * Down to which scale is a generated field the same field as the truth?  For a pair of square fields a, b (N x N as above, read
+ * through two independent EOF descriptors: each side has its own layout and dtype), A = FFT2(a), B = FFT2(b):
+ *   Paa[u][v] = |A|^2 / N^2,  Pbb[u][v] = |B|^2 / N^2,  Cab[u][v] = Re(A conj(B)) / N^2 = (A.re B.re + A.im B.im) / N^2
+ * averaged over the rings of dg_rapsd (the same ring test, counts = dg_rapsd_ring_counts, corners dropped).  Output per
+ * (field, channel): three ring means [3][K], K = N/2 + 1, plane 0 = Paa, 1 = Pbb, 2 = Cab.  The imaginary part of the cross
+ * spectrum is not stored: rings are symmetric under (u, v) -> (-u, -v), so for real fields it sums to zero.  From the planes
+ * follow per wavenumber the coherence Cab / sqrt(Paa Pbb) and the spectrum of the error a - b, Paa + Pbb - 2 Cab.
+ * Row pass: dg_rapsd's, once per side, into two half-spectrum buffers; column pass: per slice of lines u, side a's FFT kept in
+ * LDS next to side b's, the power as fmaf(X.re, X.re, X.im * X.im) and the co-spectrum as fmaf(A.re, B.re, A.im * B.im), each
+ * times 1 / N^2 and the Hermitian weight, ring sums in fp64 in dg_rapsd's order.  Hence, bit for bit: planes 0 and 1 equal
+ * dg_rapsd of a and of b, plane 2 is symmetric in (a, b), and plane 2 of (a, a) equals plane 0.  No float atomics: every sum
+ * runs in a fixed order and two calls on the same data are bit-identical.
+ *
+ * dg_cross_rapsd_ws_bytes: workspace bytes of dg_cross_rapsd for T pairs of C channels (0 for an invalid shape); ~16 (N/2 + 1) N
+ *   bytes per field (both sides' half spectra) plus small fp64 partials.
+ * dg_cross_rapsd: per_field[t][c][plane][k] (fp64 [T][C][3][K], may be NULL) and sum[c][plane][k] = sum over t in t order (fp64
+ *   [C][3][K], may be NULL).  a and b must agree in T, C and P = N*N (DG_ERR_BAD_SHAPE otherwise; dtypes other than fp32 / bf16:
+ *   DG_ERR_BAD_DTYPE; both before any launch). */
+size_t dg_cross_rapsd_ws_bytes(int T, int C, int N);
+int dg_cross_rapsd(const dg_eof_fields* a, const dg_eof_fields* b, int N, void* ws, double* per_field, double* sum, void* stream);
+
 /* ---- Value histograms (csrc/histogram.hip) ------------------------------------------------------------------------------
  * The distribution check of a downscaling generator: per-channel histograms of real and generated fields, read in place
  * through the EOF descriptor (any T, P; NCHW fp32 / bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC
