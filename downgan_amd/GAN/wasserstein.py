@@ -148,14 +148,15 @@ class WassersteinGAN:
         return float(e._sc("gp_ret").item())
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                                  coherence=None):
+                                  coherence=None, increments=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
         ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
         mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
         ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair;
-        ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair."""
+        ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair; ``increments``: one ``increments.Increments`` fed the
+        same pair."""
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -168,11 +169,11 @@ class WassersteinGAN:
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
             return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
-                                  coherence=coherence)
+                                  coherence=coherence, increments=increments)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
         return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
-                              coherence=coherence)
+                              coherence=coherence, increments=increments)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -211,6 +212,12 @@ class WassersteinGAN:
     # summary["coherence"]
     log_coherence = False
     coherence_threshold = 0.5
+    # opt-in: increment histograms of the same (real, generated) pairs -- structure functions, flatness and skewness per
+    # separation and direction, W1 / KS distances of the increment distributions (exact integer tables on the device), their
+    # summary reported per epoch in summary["increments"]; increment_spec None = increments.IncrementSpec.zscore(n_predictands)
+    log_increments = False
+    increment_spec = None
+    increment_results = None     # the last epoch's {"train" / "test": increments.IncrementResult} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -247,6 +254,12 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return ValueJoint(spec, device=dev)
 
+    def _increment_acc(self):
+        from ..increments import Increments, IncrementSpec
+        spec = self.increment_spec if self.increment_spec is not None else IncrementSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return Increments(spec, device=dev)
+
     def _coherence_acc(self, fine):
         from ..spectra import CrossSpectrum
         dev = self._engine.ops.device if self._engine is not None else self.G.device
@@ -254,7 +267,7 @@ class WassersteinGAN:
 
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -287,6 +300,11 @@ class WassersteinGAN:
             if part not in c:
                 c[part] = self._coherence_acc(fine)
             kw["coherence"] = c[part]
+        if self.log_increments:
+            i = acc.setdefault("increments", {})
+            if part not in i:
+                i[part] = self._increment_acc()
+            kw["increments"] = i[part]
         return kw
 
     def _coherence_summary(self, acc):
@@ -300,6 +318,13 @@ class WassersteinGAN:
         return {"real": s[:, 0].tolist(), "fake": s[:, 1].tolist(), "co": s[:, 2].tolist(), "coherence": coh.tolist(),
                 "rel_error": relative_error_spectrum(s).tolist(), "k_eff": [int(k) for k in k_eff],
                 "wavelength_px": [float(w) for w in wavelength_px(k_eff, acc.N)], "fields": acc.count}
+
+    def _increment_summary(self, part, acc):
+        """The JSON-serialisable summary of one part's accumulator (counts summed exactly, moments in fp64, over the data-parallel
+        ranks first); the IncrementResult is kept in ``increment_results``."""
+        res = acc.reduce_(self.dist).result()
+        self.increment_results[part] = res
+        return res.summary()
 
     def _joint_summary(self, part, acc):
         """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
@@ -385,7 +410,7 @@ class WassersteinGAN:
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
         if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
-                or self.log_coherence):
+                or self.log_coherence or self.log_increments):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -405,6 +430,9 @@ class WassersteinGAN:
                 summary["joint"] = {k: self._joint_summary(k, v) for k, v in acc.get("joint", {}).items()}
             if self.log_coherence:
                 summary["coherence"] = {k: self._coherence_summary(v) for k, v in acc.get("coherence", {}).items()}
+            if self.log_increments:
+                self.increment_results = {}
+                summary["increments"] = {k: self._increment_summary(k, v) for k, v in acc.get("increments", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

@@ -82,6 +82,7 @@ HIST_MAX_BINS, HIST_MAX_OUT = 4096, EOF_MAX_C + 1
 GRID_MAX_THR = 4
 FSS_MAX_THR, FSS_MAX_SCALES, FSS_MAX_SIDE = 4, 8, 2048
 HIST2D_MAX_PAIRS, HIST2D_MAX_CELLS, HIST2D_MAX_SECTORS = 8, 16384, 72
+INCR_MAX_LAGS, INCR_MAX_LAG, INCR_MAX_BINS, INCR_MAX_SIDE = 8, 256, 512, 2048
 
 
 class EofFields(C.Structure):
@@ -114,6 +115,12 @@ class Hist2dSpec(C.Structure):
     _fields_ = [("npairs", C.c_int), ("speed_u", C.c_int), ("speed_v", C.c_int), ("nsec", C.c_int), ("calm", C.c_float),
                 ("tan_k", C.c_float * (HIST2D_MAX_SECTORS // 4)), ("scale", C.c_float * EOF_MAX_C),
                 ("offset", C.c_float * EOF_MAX_C), ("ax", (Hist2dAxis * 2) * HIST2D_MAX_PAIRS)]
+
+
+class IncrSpec(C.Structure):
+    _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nlag", C.c_int), ("nbins", C.c_int),
+                ("lag", C.c_int * INCR_MAX_LAGS), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
+                ("lo", (C.c_float * INCR_MAX_LAGS) * HIST_MAX_OUT), ("inv_w", (C.c_float * INCR_MAX_LAGS) * HIST_MAX_OUT)]
 
 
 MINMAX_PARTS = 256
@@ -201,9 +208,13 @@ _PROTOS = {
     "dg_hist2d_ws_bytes": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(Hist2dSpec)],
     "dg_hist2d": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(Hist2dSpec), _vp, _vp, _vp],
     "dg_hist2d_host_bins": [C.POINTER(Hist2dSpec), _vp, _vp, _i, _i64, _vp],
+    "dg_incr_ws_bytes": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(IncrSpec)],
+    "dg_incr": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(IncrSpec), _vp, _vp, _vp, _vp, _vp],
+    "dg_incr_host": [C.POINTER(IncrSpec), _vp, _i, _i, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
-             "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+             "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t,
+             "dg_incr_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

@@ -1,5 +1,6 @@
 // The value transform, the bin rules and the load-mode rule shared by the value histograms (histogram.hip), the per-gridpoint
-// statistics (gridstats.hip) and the joint histograms (joint.hip): all read fields through dg_eof_fields and must see the same output values y bit for bit.
+// statistics (gridstats.hip), the joint histograms (joint.hip) and the increment histograms (increments.hip): all read fields
+// through dg_eof_fields and must see the same output values y bit for bit.
 #pragma once
 #include <stdint.h>
 
@@ -17,13 +18,21 @@ __host__ __device__ inline float hist_speed(float u, float v) {
   const float vv = v * v;
   return __builtin_sqrtf(uu + vv);
 }
+// The increment of the increment histograms (increments.hip): one correctly rounded fp32 subtraction of two already rounded y,
+// never contracted with the affine that made them.
+__host__ __device__ inline float hist_diff(float y1, float y0) {
+#pragma clang fp contract(off)
+  const float d = y1 - y0;
+  return d;
+}
 // The bin rule of the definition: each line is one correctly rounded fp32 operation.
 __host__ __device__ inline int hist_bin(float y, float lo, float inv_w, int nbins) {
 #pragma clang fp contract(off)
   const float d = y - lo;
   const float t = d * inv_w;
-  const int b = t < 0.f ? 0 : t >= (float)nbins ? nbins + 1 : 1 + (int)t;   // selects, not branches
-  return t != t ? nbins + 2 : b;
+  const bool inner = t >= 0.f && t < (float)nbins;                          // false for NaN
+  const int b = t < 0.f ? 0 : t >= (float)nbins ? nbins + 1 : 1 + (int)(inner ? t : 0.f);   // selects, not branches; only an
+  return t != t ? nbins + 2 : b;                                            // in-range t is converted (anything else is undefined in C++)
 }
 // The direction rule of the joint histograms (include/downgan_hip.h "Joint histograms", steps 1-8): the index of the sector the
 // wind (yu, yv) of speed s comes from; K = nsec / 4, tan_k[k] = fp32(tan(k pi / (4 K))), k = 1 .. K-1.  No atan2: compares of

@@ -927,6 +927,30 @@ class HipOps:
         check(self.lib.dg_hist2d(C.byref(fa), C.byref(fb) if fb is not None else None, C.byref(spec), _ptr(ws), _ptr(counts),
                                  self._stream()), "dg_hist2d")
 
+    # ------------------------------------------------------------------ increment histograms (csrc/increments.hip)
+    def incr_ws_bytes(self, fa, fb, H, W, spec):
+        """Workspace bytes of one dg_incr call over the descriptors ``fa`` (and ``fb``, or None) of H x W fields with the
+        _lib.IncrSpec ``spec`` (0: invalid)."""
+        return int(self.lib.dg_incr_ws_bytes(C.byref(fa), C.byref(fb) if fb is not None else None, int(H), int(W), C.byref(spec)))
+
+    def incr(self, fa, fb, H, W, spec, counts, finite, moments):
+        """Accumulate the increment histograms of the H x W fields of ``fa`` (eof_fields; ``fb``: the second series, or None)
+        under ``spec`` (_lib.IncrSpec): counts int64 [nser, nout, 2, nlag, nbins + 3] +=, finite int64 [nser, nout, 2, nlag] +=,
+        moments fp64 [nser, nout, 2, nlag, 6] += (nser = 2 with ``fb``).  The workspace is cached on this object."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        rows = (2 if fb is not None else 1) * nout * 2 * spec.nlag
+        for out, dt, n in ((counts, torch.int64, rows * (spec.nbins + 3)), (finite, torch.int64, rows), (moments, torch.float64, rows * 6)):
+            assert out.dtype == dt and out.is_contiguous() and out.numel() == n and out.is_cuda, (out.dtype, out.shape, n)
+        assert fb is None or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.incr_ws_bytes(fa, fb, H, W, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, H, W, spec.nlag, spec.nbins)
+        ws = getattr(self, "_incr_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._incr_ws = ws = None
+            self._incr_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_incr(C.byref(fa), C.byref(fb) if fb is not None else None, int(H), int(W), C.byref(spec), _ptr(ws),
+                               _ptr(counts), _ptr(finite), _ptr(moments), self._stream()), "dg_incr")
+
     # ------------------------------------------------------------------ per-gridpoint statistics (csrc/gridstats.hip)
     def gridstats_ws_bytes(self, f, paired, spec):
         """Workspace bytes of one dg_gridstats call over the descriptor ``f`` (one series, or with ``paired`` two) with the

@@ -717,6 +717,56 @@ size_t dg_hist2d_ws_bytes(const dg_eof_fields* a, const dg_eof_fields* b, const 
 int dg_hist2d(const dg_eof_fields* a, const dg_eof_fields* b, const dg_hist2d_spec* s, void* ws, int64_t* counts, void* stream);
 int dg_hist2d_host_bins(const dg_hist2d_spec* s, const float* xa, const float* xb, int C, int64_t n, int32_t* bins);
 
+/* ---- Increment histograms (csrc/increments.hip) -----------------------------------------------------------------------------
+ * Is the generated field as intermittent as the real one: the distributions of the spatial increments d_r y = y(x + r) - y(x) per
+ * separation r, from which follow the structure functions S_p(r), the flatness S_4 / S_2^2 (3 for a Gaussian, growing towards
+ * small r in real wind), the skewness, the scaling exponents and, at r = 1, the gradient distribution.  S_2 is the only one of
+ * these the spectrum already determines.  Fields are H x W, read through the EOF descriptor with P = H*W, p = h*W + w; series a
+ * (real) is required, series b (generated) is optional, of equal T, C, P with its own layout and dtype (NCHW fp32 / bf16, the
+ * resident feed's [n, H, W, c] store, the generator's padded NHWC output).  The output values y are those of the value
+ * histograms (the same code, csrc/hist_common.h), every fp32 operation rounded once, never contracted:
+ *   y_c = (x_c * scale[c]) + offset[c]
+ *   s   = sqrt(y_u * y_u + y_v * y_v)                       speed_u >= 0: appended as output channel C (nout = C + 1)
+ * For output channel j and lag r = lag[l]:
+ *   direction 0 (along w):  d = fp32(y[t,h,w+r] - y[t,h,w])   for 0 <= w < W - r
+ *   direction 1 (along h):  d = fp32(y[t,h+r,w] - y[t,h,w])   for 0 <= h < H - r
+ * one correctly rounded fp32 subtraction of the already rounded y (hist_diff), never contracted with the affine.  No wrap-around;
+ * a lag >= the extent contributes nothing in that direction and is not an error.
+ *   bin     = hist_bin(d, lo[j][l], inv_w[j][l], nbins): index 0 underflow, 1 .. nbins interior, nbins + 1 overflow (+-inf land
+ *             in under / overflow), nbins + 2 NaN (a NaN operand gives a NaN d, and so does inf - inf)
+ *   counts  int64 [nser][nout][2][nlag][nbins + 3]
+ *   finite  int64 [nser][nout][2][nlag]       the number of finite d
+ *   moments fp64  [nser][nout][2][nlag][6]    over the finite d, u = (double)d:  sum u, |u|, u^2, u^3, |u|^3, u^4, formed as
+ *                                             u2 = u*u, u3 = u2*u, u4 = u2*u2
+ * nser is 1 (b NULL) or 2.  All three ACCUMULATE (the caller zeroes them).  A workgroup stages a tile of the transformed values
+ * of one output channel in LDS with a halo of the largest lag of the direction it serves (long row segments for direction 0,
+ * 64-column strips for direction 1), so both operands of every increment come from LDS; the counts come from uint32 LDS tables
+ * (ds_add_u32) flushed with 64-bit integer atomics: exact for any T * P and independent of arrival order.  The moments go through
+ * per-workgroup partials summed in a fixed order.  No float atomics: two calls on the same data are bit-identical in all three
+ * outputs.  When the tables of a spec do not fit beside the tile, the output channels are cut into groups, one launch each.
+ *
+ * dg_incr_ws_bytes: workspace bytes of one call (0 for an invalid call).
+ * dg_incr: rejected before any launch (DG_ERR_BAD_SHAPE; DG_ERR_BAD_DTYPE for a dtype other than fp32 / bf16): a NULL pointer,
+ *   P != H*W, H or W outside 1 .. DG_INCR_MAX_SIDE, series that differ in T, C or P, nlag or nbins out of range, lags unsorted or
+ *   out of range, a non-finite lo, inv_w, scale or offset, inv_w <= 0, speed channels that do not exist.
+ * dg_incr_host: host-side, the same definition for one field of one series, planar fp32 [C][H][W]; adds (+=) into the slices of
+ *   one series: counts [nout][2][nlag][nbins + 3], finite [nout][2][nlag], moments [nout][2][nlag][6]. */
+#define DG_INCR_MAX_LAGS 8
+#define DG_INCR_MAX_LAG  256
+#define DG_INCR_MAX_BINS 512
+#define DG_INCR_MAX_SIDE 2048
+typedef struct dg_incr_spec {
+  int speed_u, speed_v;            /* input channels of the speed channel, or -1, -1: none */
+  int nlag, nbins;                 /* 1 .. MAX each */
+  int lag[DG_INCR_MAX_LAGS];       /* 1 <= lag <= DG_INCR_MAX_LAG, strictly increasing */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float lo[DG_HIST_MAX_OUT][DG_INCR_MAX_LAGS], inv_w[DG_HIST_MAX_OUT][DG_INCR_MAX_LAGS];  /* finite; inv_w > 0 */
+} dg_incr_spec;
+size_t dg_incr_ws_bytes(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_incr_spec* s);
+int dg_incr(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_incr_spec* s, void* ws,
+            int64_t* counts, int64_t* finite, double* moments, void* stream);
+int dg_incr_host(const dg_incr_spec* s, const float* x, int C, int H, int W, int64_t* counts, int64_t* finite, double* moments);
+
 #ifdef __cplusplus
 }
 #endif

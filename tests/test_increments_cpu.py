@@ -1,0 +1,594 @@
+"""Increment histograms without a GPU: the library's host reference (dg_incr_host) against a numpy float32 restatement of the
+definition -- every multiply, add and subtract rounded to float32 -- on adversarial values (differences on bin edges, inf - inf,
+NaN, signed zeros, subnormals), with lags equal to W - 1, equal to W and above H; the moments against math.fsum of the float64
+terms to 1e-12 * sum |term| (fp64 unit round-off 1.1e-16 times the longest addition chain at these sizes, < 10^4 terms, the rule
+test_histograms_gpu.py applies to dg_hist's sums); known answers (a ramp, a constant field, table totals, transposition);
+argument checks that fire before any library call; the ABI surface and the struct layout; the derived statistics on hand-built
+tables; and the trainer's opt-in hook on the emulated ops (a test-local op class implements ``incr`` by the restatement), in one
+process, in the frequency-separation trainer, and over 2 gloo ranks."""
+import ctypes as C
+import json
+import math
+import os
+import re
+import shutil
+import subprocess
+import tempfile
+import types
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from downgan_amd import _lib, increments
+from downgan_amd.increments import IncrementResult, Increments, IncrementSpec
+
+from .test_histograms_cpu import F32, SPECIAL, _loaders, edge_values
+from .test_joint_cpu import bin_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ------------------------------------------------------------------------------------------------- the definition in numpy
+def view(s, Cn):
+    """A dg_incr_spec (ctypes) as numpy float32 values."""
+    nout = Cn + (s.speed_u >= 0)
+    return types.SimpleNamespace(
+        C=Cn, nout=nout, su=s.speed_u, sv=s.speed_v, nlag=s.nlag, nbins=s.nbins, lags=list(s.lag[:s.nlag]),
+        scale=np.array(s.scale[:Cn], dtype=F32), offset=np.array(s.offset[:Cn], dtype=F32),
+        lo=np.array([list(r) for r in s.lo], dtype=F32), inv_w=np.array([list(r) for r in s.inv_w], dtype=F32))
+
+
+def transform_ref(v, x):
+    """x float32 [T, C, H, W] -> the output values float32 [T, nout, H, W] (affine, then the speed of the pair)."""
+    x = np.asarray(x, dtype=F32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        y = (x * v.scale[None, :, None, None]).astype(F32)
+        y = (y + v.offset[None, :, None, None]).astype(F32)
+        if v.su >= 0:
+            a, b = y[:, v.su], y[:, v.sv]
+            s = np.sqrt(((a * a).astype(F32) + (b * b).astype(F32)).astype(F32)).astype(F32)
+            y = np.concatenate([y, s[:, None]], axis=1)
+    return y
+
+
+def diffs_ref(y, j, d, r):
+    """The increments float32 (flat) of output channel j in direction d at lag r: one float32 subtraction each."""
+    T, _, H, W = y.shape
+    with np.errstate(over="ignore", invalid="ignore"):
+        if d == 0:
+            return (y[:, j, :, r:] - y[:, j, :, :max(W - r, 0)]).astype(F32).reshape(-1) if r < W else np.zeros(0, F32)
+        return (y[:, j, r:, :] - y[:, j, :max(H - r, 0), :]).astype(F32).reshape(-1) if r < H else np.zeros(0, F32)
+
+
+def terms_ref(d):
+    """float64 [6, n]: u, |u|, u^2, u^3, |u|^3, u^4 of the finite increments, formed as u2 = u u, u3 = u2 u, u4 = u2 u2."""
+    u = d[np.isfinite(d)].astype(np.float64)
+    u2 = u * u
+    u3 = u2 * u
+    return np.stack([u, np.abs(u), u2, u3, np.abs(u3), u2 * u2])
+
+
+def incr_ref(v, x, exact=True):
+    """(counts int64 [nout, 2, nlag, nbins + 3], finite int64 [nout, 2, nlag], moments float64 [nout, 2, nlag, 6] by math.fsum,
+    scale float64 [nout, 2, nlag, 6] = fsum |term|) of one series x float32 [T, C, H, W] under the spec view v.  exact False (the
+    larger fields of the GPU tests): numpy's pairwise sum in long double instead of math.fsum -- its error, ~1e-19 sum |term|, is
+    seven orders below the 1e-12 sum |term| the moments are held to."""
+    total = (lambda r: math.fsum(r.tolist())) if exact else (lambda r: float(r.astype(np.longdouble).sum()))
+    y = transform_ref(v, x)
+    shape = (v.nout, 2, v.nlag)
+    counts = np.zeros(shape + (v.nbins + 3,), dtype=np.int64)
+    finite = np.zeros(shape, dtype=np.int64)
+    moments, scale = np.zeros(shape + (6,)), np.zeros(shape + (6,))
+    for j, d, l in np.ndindex(*shape):
+        dd = diffs_ref(y, j, d, v.lags[l])
+        if dd.size:
+            counts[j, d, l] = np.bincount(bin_ref(dd, v.lo[j, l], v.inv_w[j, l], v.nbins), minlength=v.nbins + 3)
+        t = terms_ref(dd)
+        finite[j, d, l] = t.shape[1]
+        moments[j, d, l] = [total(r) for r in t]
+        scale[j, d, l] = [total(np.abs(r)) for r in t]
+    return counts, finite, moments, scale
+
+
+def spec_ref(spec, x, exact=True):
+    return incr_ref(view(spec.struct(), spec.C), x, exact)
+
+
+def assert_tables(got, ref, what=""):
+    """got (counts, finite, moments) against ref (counts, finite, moments, scale): integers exact, moments to 1e-12 sum |term|."""
+    np.testing.assert_array_equal(got[0], ref[0], err_msg=f"counts {what}")
+    np.testing.assert_array_equal(got[1], ref[1], err_msg=f"finite {what}")
+    err = np.abs(np.asarray(got[2]) - ref[2])
+    assert np.all(err <= 1e-12 * ref[3]), (what, float(err.max()), np.argwhere(err > 1e-12 * ref[3])[:4].tolist())
+
+
+def totals(T, H, W, lags):
+    """int64 [2, nlag]: the number of increments per direction and lag."""
+    return np.array([[T * H * max(0, W - r) for r in lags], [T * max(0, H - r) * W for r in lags]], dtype=np.int64)
+
+
+# ------------------------------------------------------------------------------------------------- the host reference
+def adversarial(T, H, W, seed=0):
+    """float32 [T, 2, H, W]: zeros at the even columns (rows) and bin edges with their fp32 neighbours and the special values at
+    the odd ones, so that the lag-1 differences are those values themselves (on the edges of the bins of a spec with range 2 and
+    64 bins), and the larger lags give edge - edge, inf - inf, inf - finite, NaN, +-0 and subnormal differences."""
+    rng = np.random.default_rng(seed)
+    vals = np.concatenate([edge_values(-2.0, 1 / 16, 64), np.tile(SPECIAL, 8), -edge_values(-2.0, 1 / 16, 64)]).astype(F32)
+    x = np.zeros((T, 2, H, W), F32)
+    x[:, 0, :, 1::2] = rng.choice(vals, x[:, 0, :, 1::2].shape)
+    x[:, 1, 1::2, :] = rng.choice(vals, x[:, 1, 1::2, :].shape)
+    x[:, 1, 0, :] = -0.0
+    return x
+
+
+@pytest.mark.parametrize("shape", [(2, 9, 26), (1, 7, 13), (3, 41, 37)])
+def test_host_reference_on_adversarial_values(shape):
+    T, H, W = shape
+    lags = sorted({1, 2, 3, H, W - 1, W, max(H, W) + 4} - {0})[:8]               # W - 1, W, and above H (and above W)
+    assert W - 1 in lags and W in lags and any(r > H for r in lags)
+    x = adversarial(T, H, W, seed=H)
+    for speed in (None, (0, 1), (1, 0)):
+        spec = IncrementSpec(2, speed=speed, lags=lags, nbins=64, ranges=2.0)
+        assert float(spec.inv_w[0, 0]) == 16.0
+        got = increments.host_increments(spec, x)
+        ref = spec_ref(spec, x)
+        assert_tables(got, ref, f"{shape} speed {speed}")
+        nout = 2 + (speed is not None)
+        np.testing.assert_array_equal(got[0].sum(axis=-1), np.broadcast_to(totals(T, H, W, lags), (nout, 2, len(lags))))
+        assert got[0][..., -1].sum() > 0 and got[0][..., 0].sum() > 0 and got[0][..., -2].sum() > 0     # NaN, under-, overflow
+    # an affine transform with rounding in it
+    spec = IncrementSpec(2, scale=[0.3, 1.7], offset=[0.1, -0.7], speed=(0, 1), lags=lags, nbins=33, ranges=[[1.0] * len(lags),
+                         [0.37] * len(lags), [2.5] * len(lags)])
+    assert_tables(increments.host_increments(spec, x), spec_ref(spec, x), f"{shape} affine")
+
+
+def test_gaussian_fields_and_accumulation():
+    rng = np.random.default_rng(3)
+    x = (rng.standard_normal((3, 2, 40, 37)) * 1.5).astype(F32)
+    spec = IncrementSpec.zscore(2, lags=(1, 2, 4, 8, 16, 32, 36, 39), nbins=128)
+    got = increments.host_increments(spec, x)
+    assert_tables(got, spec_ref(spec, x))
+    parts = [increments.host_increments(spec, x[t:t + 1]) for t in range(3)]
+    np.testing.assert_array_equal(sum(p[0] for p in parts), got[0])
+    np.testing.assert_array_equal(sum(p[1] for p in parts), got[1])
+
+
+def test_ramp_and_constant_field():
+    H, W, lags = 12, 40, (1, 2, 4, 8, 39, 40)
+    spec = IncrementSpec(1, speed=None, lags=lags, nbins=64, ranges=16.0)       # bin width 0.5
+    ramp = np.broadcast_to((0.25 * np.arange(W, dtype=F32))[None, None, None, :], (2, 1, H, W)).copy()
+    c, f, m = increments.host_increments(spec, ramp)
+    tot = totals(2, H, W, lags)
+    for l, r in enumerate(lags):
+        k = 1 + int((0.25 * r + 16.0) * 2.0)
+        assert c[0, 0, l, k] == tot[0, l] and c[0, 0, l].sum() == tot[0, l], (r, k)
+        assert c[0, 1, l, 1 + 32] == tot[1, l] and c[0, 1, l].sum() == tot[1, l], r
+    np.testing.assert_array_equal(f[0], tot)
+    res = IncrementResult(spec, c[None], f[None], m[None], 2, H, W)
+    np.testing.assert_allclose(res.structure(1)[0, 0, 0, :5], [0.25 * r for r in lags[:5]], rtol=1e-15)
+    np.testing.assert_allclose(res.exponents(2)[0, 0, 0], 2.0, rtol=1e-12)      # S_2 = (r / 4)^2
+    assert np.isnan(res.structure(2)[0, 0, 0, 5])                               # lag = W: no increment
+    const = np.full((2, 1, H, W), 1.25, F32)
+    c, f, m = increments.host_increments(spec, const)
+    res = IncrementResult(spec, c[None], f[None], m[None], 2, H, W)
+    s = res.summary()
+    json.dumps(s, allow_nan=False)                                              # undefined values are None, never NaN
+    assert s["real"]["flatness"] == [[[None] * len(lags)] * 2] and s["real"]["skewness"] == [[[None] * len(lags)] * 2]
+    assert s["real"]["structure"]["2"][0][0][:5] == [0.0] * 5 and s["real"]["structure"]["2"][0][0][5] is None
+    assert s["real"]["exponent_2"] == [[None, None]]
+
+
+def test_transposition_swaps_the_directions():
+    rng = np.random.default_rng(5)
+    x = adversarial(2, 14, 23, seed=9) + (rng.standard_normal((2, 2, 14, 23)) * 0.5).astype(F32)
+    spec = IncrementSpec(2, lags=(1, 3, 13, 14, 22, 23), nbins=50, ranges=3.0)
+    a = increments.host_increments(spec, x)
+    b = increments.host_increments(spec, np.ascontiguousarray(x.transpose(0, 1, 3, 2)))
+    np.testing.assert_array_equal(a[0][:, 0], b[0][:, 1])
+    np.testing.assert_array_equal(a[0][:, 1], b[0][:, 0])
+    np.testing.assert_array_equal(a[1][:, ::-1], b[1])
+    ref = spec_ref(spec, x)
+    assert np.all(np.abs(a[2][:, ::-1] - b[2]) <= 2e-12 * ref[3][:, ::-1])     # the same terms in another order
+
+
+# ------------------------------------------------------------------------------------------------- argument checks
+def _no_library(monkeypatch):
+    def boom(*a, **k):
+        raise AssertionError("library or device touched before the arguments were checked")
+    from downgan_amd import backend
+    monkeypatch.setattr(_lib, "lib", boom)
+    monkeypatch.setattr(backend, "make_ops", boom)
+    monkeypatch.setattr(increments, "_ops", {})
+
+
+@pytest.mark.parametrize("kw,match", [
+    (dict(C=0), "C <="), (dict(C=9), "C <="), (dict(C=1), "speed"), (dict(C=3, speed=(0, 3)), "speed"),
+    (dict(C=2, lags=()), "lags"), (dict(C=2, lags=range(1, 10)), "lags"), (dict(C=2, lags=(0, 1)), r"\[1, 256\]"),
+    (dict(C=2, lags=(1, 257)), r"\[1, 256\]"), (dict(C=2, lags=(1, 2.5)), "integers"), (dict(C=2, lags=(2, 2)), "increasing"),
+    (dict(C=2, lags=(4, 2)), "increasing"), (dict(C=2, nbins=0), "nbins"), (dict(C=2, nbins=513), "nbins"),
+    (dict(C=2, nbins=2.5), "nbins"), (dict(C=2, ranges=0.0), "> 0"), (dict(C=2, ranges=-1.0), "> 0"),
+    (dict(C=2, ranges=np.inf), "finite"), (dict(C=2, ranges=[1.0, 2.0]), "ranges"), (dict(C=2, ranges=np.ones((2, 8))), "ranges"),
+    (dict(C=2, ranges=1e-44, nbins=512), "bin width"), (dict(C=2, scale=[1.0]), "scale"), (dict(C=2, offset=[0.0, np.nan]), "finite"),
+    (dict(C=2, names=["u", "v"]), "names"),
+])
+def test_spec_is_checked(monkeypatch, kw, match):
+    _no_library(monkeypatch)
+    with pytest.raises(ValueError, match=match):
+        IncrementSpec(**kw)
+
+
+@pytest.mark.parametrize("a,b,kw,err,match", [
+    (torch.zeros(2, 3, 8, 8), None, {}, ValueError, "C = 2"),
+    (torch.zeros(2, 2, 8, 8), torch.zeros(3, 2, 8, 8), {}, ValueError, "length"),
+    (torch.zeros(2, 2, 8, 8), torch.zeros(2, 2, 8, 9), {}, ValueError, "grid"),
+    (torch.zeros(2, 2, 8, 8), torch.zeros(2, 3, 8, 8), {}, ValueError, "channels"),
+    (torch.zeros(2, 2, 8, 8), torch.zeros(2, 8, 8, 4), {"nhwc": (False, True), "channels": 5}, ValueError, "channels"),
+    (torch.zeros(2, 2, 8, 8, dtype=torch.float64), None, {}, TypeError, "fp32 or bf16"),
+    (torch.zeros(2, 2, 8, 8), torch.zeros(2, 2, 8, 8, dtype=torch.float16), {}, TypeError, "fp32 or bf16"),
+    (np.zeros((2, 2, 8, 8), np.float32), None, {}, TypeError, "tensor"),
+    (torch.zeros(2, 8, 8), None, {}, ValueError, "shape"),
+    (torch.zeros(0, 2, 8, 8), None, {}, ValueError, "at least one"),
+    (torch.zeros(1, 2, 2, 2049), None, {}, ValueError, "2048"),
+    (torch.zeros(2, 2, 8, 8), None, {"nhwc": (True, False, True)}, ValueError, "nhwc"),
+])
+def test_arguments_are_checked_before_any_library_call(monkeypatch, a, b, kw, err, match):
+    _no_library(monkeypatch)
+    spec = IncrementSpec.zscore(2)
+    with pytest.raises(err, match=match):
+        increments.increments(a, b, spec, **kw)
+    acc = Increments(spec, device="cpu")
+    with pytest.raises(err, match=match):
+        acc.add(a, b, **kw)
+    for n in (0, 3, -1):
+        with pytest.raises(ValueError, match="n_valid"):
+            acc.add(torch.zeros(2, 2, 8, 8), n_valid=n)
+    with pytest.raises(TypeError, match="IncrementSpec"):
+        increments.increments(torch.zeros(1, 2, 4, 4), spec=[1, 2])
+    with pytest.raises(TypeError, match="IncrementSpec"):
+        Increments(None, device="cpu")
+    with pytest.raises(ValueError, match=r"C = 2, H, W"):
+        increments.host_increments(spec, np.zeros((1, 3, 4, 4), F32))
+
+
+def test_constructors():
+    z = IncrementSpec.zscore(2)
+    assert z.lags == (1, 2, 4, 8, 16, 32, 64, 128) == increments.DEFAULT_LAGS and z.nbins == 128 and z.speed == (0, 1)
+    assert z.names == ["ch0", "ch1", "speed"] and z.nout == 3 and z.ranges.shape == (3, 8)
+    np.testing.assert_array_equal(z.ranges[0], np.array([8.0 * min(1.0, (r / 64) ** (1 / 3)) for r in z.lags]).astype(F32))
+    np.testing.assert_array_equal(z.lo, -z.ranges)
+    np.testing.assert_array_equal(z.inv_w, (128 / (2.0 * z.ranges.astype(np.float64))).astype(F32))     # rounded once
+    assert IncrementSpec.zscore(1).speed is None and IncrementSpec.zscore(1).nout == 1
+    s = z.struct()
+    assert (s.speed_u, s.speed_v, s.nlag, s.nbins) == (0, 1, 8, 128) and list(s.lag) == list(z.lags)
+    assert s.lo[2][3] == -z.ranges[2, 3] and s.inv_w[1][7] == z.inv_w[1, 7] and s.scale[1] == 1.0 and s.offset[1] == 0.0
+    stats = {"u10": (0.5, 3.0), "v10": (-0.25, 2.0), "t2m": (280.0, 10.0)}
+    p = IncrementSpec.physical(stats, ["t2m", "u10", "v10"], 20.0, lags=(1, 64))
+    assert p.speed == (1, 2) and p.names == ["t2m", "u10", "v10", "speed"] and p.scale.tolist() == [10.0, 3.0, 2.0]
+    assert p.offset.tolist() == [280.0, 0.5, -0.25] and p.ranges[0].tolist() == [5.0, 20.0]
+    assert p == IncrementSpec.physical(stats, ["t2m", "u10", "v10"], 20.0, lags=(1, 64)) and p != z and z == IncrementSpec.zscore(2)
+    assert z != IncrementSpec.zscore(2, nbins=64) and IncrementSpec.physical(stats, ["t2m"], 5.0, speed=None).names == ["t2m"]
+    assert z.centres(0, 7)[0] == -8.0 + 0.5 * 16 / 128 and z.width()[0, 7] == 0.125
+
+
+# ------------------------------------------------------------------------------------------------- the ABI
+def test_header_declares_and_library_exports_the_increment_abi():
+    src = open(os.path.join(ROOT, "include", "downgan_hip.h")).read()
+    for name, val in (("LAGS", 8), ("LAG", 256), ("BINS", 512), ("SIDE", 2048)):
+        assert re.search(rf"#define DG_INCR_MAX_{name}\s+{val}\b", src), name
+    for sym in ("dg_incr_ws_bytes", "dg_incr", "dg_incr_host"):
+        assert re.search(rf"\b{sym}\s*\(", src), sym
+        assert sym in _lib.EXPORTS
+        assert hasattr(_lib.lib(), sym)
+    assert (_lib.INCR_MAX_LAGS, _lib.INCR_MAX_LAG, _lib.INCR_MAX_BINS, _lib.INCR_MAX_SIDE) == (8, 256, 512, 2048)
+    assert (increments.LAGS_MAX, increments.LAG_MAX, increments.BINS_MAX, increments.SIDE_MAX) == (8, 256, 512, 2048)
+    common = open(os.path.join(ROOT, "downgan_amd", "csrc", "hist_common.h")).read()
+    assert re.search(r"inline float hist_diff\(float \w+, float \w+\) \{\s*#pragma clang fp contract\(off\)", common)
+
+
+def test_struct_layout_matches_the_header(tmp_path):
+    if shutil.which("gcc") is None:
+        pytest.skip("gcc not available")
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{ROOT}/include/downgan_hip.h"', 'int main(void) {',
+             '  printf("dg_incr_spec %zu\\n", sizeof(dg_incr_spec));']
+    lines += [f'  printf("dg_incr_spec.{f} %zu\\n", offsetof(dg_incr_spec, {f}));' for f, _ in _lib.IncrSpec._fields_]
+    lines += ['  return 0;', '}']
+    (tmp_path / "l.c").write_text("\n".join(lines))
+    subprocess.run(["gcc", "-std=c99", "-o", str(tmp_path / "l"), str(tmp_path / "l.c")], check=True)
+    got = dict(l.split() for l in subprocess.run([str(tmp_path / "l")], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert int(got["dg_incr_spec"]) == C.sizeof(_lib.IncrSpec)
+    for f, _ in _lib.IncrSpec._fields_:
+        assert int(got[f"dg_incr_spec.{f}"]) == getattr(_lib.IncrSpec, f).offset, f
+
+
+def test_abi_rejects_bad_arguments_without_launching():
+    lib = _lib.lib()
+    ok = dict(base=0x1000, dtype=_lib.DG_F32, T=4, C=2, P=100, ld_t=200, ld_c=100, ld_p=1)
+    f = lambda **kw: C.byref(_lib.EofFields(**dict(ok, **kw)))
+
+    def spec(lag=None, lo=None, inv_w=None, scale=None, offset=None, **kw):
+        s = IncrementSpec.zscore(2).struct()
+        for k, v in kw.items():
+            setattr(s, k, v)
+        for l, r in (lag or {}).items():
+            s.lag[l] = r
+        for (j, l), v in (lo or {}).items():
+            s.lo[j][l] = v
+        for (j, l), v in (inv_w or {}).items():
+            s.inv_w[j][l] = v
+        for c, v in (scale or {}).items():
+            s.scale[c] = v
+        for c, v in (offset or {}).items():
+            s.offset[c] = v
+        return C.byref(s)
+    ws, o1, o2, o3 = (C.c_void_p(a) for a in (0x2000, 0x3000, 0x4000, 0x5000))
+    call = lambda fa, fb, s, H=10, W=10, w=ws, c=o1, n=o2, m=o3: lib.dg_incr(fa, fb, H, W, s, w, c, n, m, None)
+    good = spec()
+    assert lib.dg_incr_ws_bytes(f(), f(), 10, 10, good) > 0 and lib.dg_incr_ws_bytes(f(), None, 10, 10, good) > 0
+    nan, inf = float("nan"), float("inf")
+    bad_specs = [spec(nlag=0), spec(nlag=9), spec(nbins=0), spec(nbins=513), spec(lag={0: 0}), spec(lag={7: 257}),
+                 spec(lag={3: 4}), spec(lag={3: 3}), spec(lag={2: 100}),                        # equal, decreasing, above the next
+                 spec(lo={(2, 7): nan}), spec(lo={(0, 0): inf}), spec(inv_w={(1, 3): 0.0}), spec(inv_w={(1, 3): -1.0}),
+                 spec(inv_w={(2, 0): inf}), spec(inv_w={(0, 0): nan}), spec(scale={1: inf}), spec(offset={0: nan}),
+                 spec(speed_u=2), spec(speed_v=-1), spec(speed_u=-1)]
+    for i, s in enumerate(bad_specs):
+        assert call(f(), f(), s) == -1, i
+        assert lib.dg_incr_ws_bytes(f(), f(), 10, 10, s) == 0, i
+    assert call(f(), None, spec(speed_u=-1, speed_v=-1)) in (0, -4)              # no speed channel: valid (no GPU here: a launch error)
+    for fa, fb, H, W in ((None, f(), 10, 10), (f(base=0), None, 10, 10), (f(), f(base=0), 10, 10), (f(C=9), None, 10, 10),
+                         (f(T=0), None, 10, 10), (f(), None, 10, 11), (f(), None, 5, 10), (f(), None, 0, 10),
+                         (f(P=2049), None, 1, 2049), (f(P=2049), None, 2049, 1),
+                         (f(), f(T=5), 10, 10), (f(), f(C=3), 10, 10), (f(), f(P=96), 10, 10)):
+        assert call(fa, fb, good, H, W) == -1, (H, W)
+        assert lib.dg_incr_ws_bytes(fa, fb, H, W, good) == 0
+    assert call(f(), f(), None) == -1
+    assert call(f(), f(), good, w=None) == -1 and call(f(), f(), good, c=None) == -1 and call(f(), f(), good, n=None) == -1
+    assert call(f(), f(), good, m=None) == -1
+    assert call(f(dtype=7), f(), good) == -2 and call(f(), f(dtype=7), good) == -2
+    x = np.zeros((2, 10, 10), F32)
+    c, n, m = np.zeros((3, 2, 8, 131), np.int64), np.zeros((3, 2, 8), np.int64), np.zeros((3, 2, 8, 6))
+    host = lambda s, xp=x.ctypes.data, H=10, W=10, cp=c.ctypes.data, np_=n.ctypes.data, mp_=m.ctypes.data: \
+        lib.dg_incr_host(s, xp, 2, H, W, cp, np_, mp_)
+    assert host(spec(nlag=0)) == -1 and host(good, xp=None) == -1 and host(good, cp=None) == -1 and host(good, np_=None) == -1
+    assert host(good, mp_=None) == -1 and host(good, H=0) == -1 and host(good, W=2049) == -1 and host(None) == -1
+    assert host(good) == 0 and c.sum() == 3 * (10 * (9 + 8 + 6 + 2) * 2)
+
+
+# ------------------------------------------------------------------------------------------------- derived statistics
+def make_result(spec, nser=2, H=64, W=64, fields=1):
+    shape = (nser, spec.nout, 2, spec.nlag)
+    return IncrementResult(spec, np.zeros(shape + (spec.nbins + 3,), np.int64), np.zeros(shape, np.int64), np.zeros(shape + (6,)),
+                           fields, H, W)
+
+
+def test_structure_functions_of_a_hand_built_table():
+    spec = IncrementSpec(1, speed=None, lags=(1, 2), nbins=4, ranges=2.0)         # bins of width 1 on [-2, 2)
+    r = make_result(spec, nser=1)
+    d = np.array([-1.5, -0.5, 0.5, 0.5, 1.5, 1.5, 1.5, 0.5])                       # eight increments at lag 1, direction 0
+    r.counts[0, 0, 0, 0] = [1, 1, 1, 3, 3, 2, 4]                                   # + one underflow, two overflows, four NaN
+    r.finite[0, 0, 0, 0] = 8
+    r.moments[0, 0, 0, 0] = [d.sum(), np.abs(d).sum(), (d ** 2).sum(), (d ** 3).sum(), (np.abs(d) ** 3).sum(), (d ** 4).sum()]
+    for p in (1, 2, 3, 4):
+        assert r.structure(p)[0, 0, 0, 0] == pytest.approx(np.mean(np.abs(d) ** p), rel=1e-15)
+        assert np.isnan(r.structure(p)[0, 0, 0, 1]) and np.isnan(r.structure(p)[0, 0, 1, 0])
+    s2 = np.mean(d ** 2)
+    assert r.skewness()[0, 0, 0, 0] == pytest.approx(np.mean(d ** 3) / s2 ** 1.5, rel=1e-15)
+    assert r.flatness()[0, 0, 0, 0] == pytest.approx(np.mean(d ** 4) / s2 ** 2, rel=1e-15)
+    x, pdf = r.pdf("real", 0, 0, 1)
+    assert x.tolist() == [-1.5, -0.5, 0.5, 1.5] and pdf.tolist() == [1 / 11, 1 / 11, 3 / 11, 3 / 11]     # 11 non-NaN, width 1
+    assert np.all(np.isnan(r.pdf(0, "ch0", 1, 2)[1]))
+    with pytest.raises(KeyError, match="lag"):
+        r.pdf(0, 0, 0, 3)
+    with pytest.raises(IndexError, match="series"):
+        r.pdf("fake", 0, 0, 1)
+    with pytest.raises(ValueError, match="real and the generated"):
+        r.w1()
+    with pytest.raises(ValueError, match="p = 1 .. 4"):
+        r.structure(5)
+
+
+def test_flatness_of_a_large_gaussian_sample():
+    """1024 x 1024 independent N(0, 1) values: the lag-r increments are N(0, 2), flatness 3, skewness 0.  The sample kurtosis of n
+    Gaussian values has standard error sqrt(24 / n) -- here n ~ 10^6, and neighbouring increments share a point, so take
+    sqrt(96 / n) ~ 0.01 -- and the bound is five of them."""
+    rng = np.random.default_rng(1)
+    x = rng.standard_normal((1, 1, 1024, 1024)).astype(F32)
+    spec = IncrementSpec(1, speed=None, lags=(1, 7, 64), nbins=64, ranges=8.0)
+    c, f, m = increments.host_increments(spec, x)
+    r = IncrementResult(spec, c[None], f[None], m[None], 1, 1024, 1024)
+    assert np.all(np.abs(r.flatness() - 3.0) < 0.05) and np.all(np.abs(r.skewness()) < 0.05)
+    np.testing.assert_allclose(r.structure(2), 2.0, rtol=0.01)
+    assert np.all(np.abs(r.exponents(2)) < 0.01)                                  # white noise: S_2 does not depend on r
+
+
+def test_exponent_of_a_power_law_and_pooling():
+    spec = IncrementSpec(2, lags=(1, 2, 4, 8, 16), nbins=8, ranges=4.0)
+    r = make_result(spec)
+    lag = np.array(spec.lags, dtype=np.float64)
+    r.finite[...] = 1000
+    r.moments[0, ..., 2] = 1000 * lag ** 0.7
+    r.moments[1, ..., 2] = 1000 * 0.5 * lag ** (2 / 3)
+    r.moments[..., 5] = 1000 * 3.0 * lag ** 1.4
+    np.testing.assert_allclose(r.exponents(2)[0], 0.7, rtol=1e-12)
+    np.testing.assert_allclose(r.exponents(2)[1], 2 / 3, rtol=1e-12)
+    np.testing.assert_allclose(r.exponents(4, lags=(2, 4, 16)), 1.4, rtol=1e-12)
+    r.finite[0, 0, 0, 0] = 0                                                       # an empty lag is left out of the fit
+    np.testing.assert_allclose(r.exponents(2)[0, 0, 0], 0.7, rtol=1e-12)
+    r.finite[0, 0, 0, 1:] = 0
+    assert np.isnan(r.exponents(2)[0, 0, 0])
+    np.testing.assert_allclose(r.flatness()[0, 1], 3.0, rtol=1e-12)
+    np.testing.assert_allclose(r.flatness_ratio()[1, 1], 3.0 * lag ** 1.4 / (0.5 * lag ** (2 / 3)) ** 2 / 3.0, rtol=1e-12)
+    # pooling: the sums and the counts are added, not the ratios
+    q = make_result(spec)
+    for (j, d), (n, s2) in {(0, 0): (100, 50.0), (1, 1): (300, 30.0), (0, 1): (10, 7.0), (1, 0): (30, 9.0)}.items():
+        q.finite[:, j, d, :] = n
+        q.moments[:, j, d, :, 2] = s2
+    np.testing.assert_allclose(q.longitudinal(2), 80.0 / 400, rtol=1e-15)
+    np.testing.assert_allclose(q.transverse(2), 16.0 / 40, rtol=1e-15)
+    assert q.longitudinal(2).shape == (2, 5)
+    with pytest.raises(ValueError, match="speed"):
+        make_result(IncrementSpec(2, speed=None)).longitudinal(2)
+
+
+def test_distances_between_the_real_and_the_generated_distributions():
+    spec = IncrementSpec(1, speed=None, lags=(1, 2), nbins=8, ranges=4.0)         # width 1
+    r = make_result(spec)
+    r.counts[0, 0, 0, 0, 4] = 10                                                   # real: all in bin [-1, 0)
+    r.counts[1, 0, 0, 0, 6] = 10                                                   # generated: two bins further
+    r.counts[:, 0, 1, 0, 3] = 7                                                    # identical
+    assert r.w1()[0, 0, 0] == pytest.approx(2.0, rel=1e-15) and r.ks()[0, 0, 0] == 1.0
+    assert r.w1()[0, 1, 0] == 0.0 and r.ks()[0, 1, 0] == 0.0
+    assert np.isnan(r.w1()[0, 0, 1]) and np.isnan(r.ks()[0, 1, 1])                 # no increments at lag 2
+    s = r.summary()
+    json.dumps(s, allow_nan=False)
+    assert s["w1"][0][0] == [2.0, None] and s["series"] == ["real", "fake"] and s["lags"] == [1, 2] and s["grid"] == [64, 64]
+
+
+# ------------------------------------------------------------------------------------------------- trainer hook, emulated
+def incr_emu_ops():
+    from oracle.emu_ops import EmuOps
+
+    class IncrEmuOps(EmuOps):
+        """The emulated ops plus dg_incr's contract by the numpy restatement."""
+
+        @staticmethod
+        def eof_fields(t, nhwc=False, channels=None):
+            Cn = (t.shape[3] if channels is None else channels) if nhwc else t.shape[1]
+            return types.SimpleNamespace(t=t, nhwc=nhwc, T=t.shape[0], C=Cn, P=t.shape[1] * t.shape[2])
+
+        def incr_ws_bytes(self, fa, fb, H, W, spec):
+            return 1
+
+        def incr(self, fa, fb, H, W, s, counts, finite, moments):
+            nchw = lambda f: (f.t[..., :f.C].permute(0, 3, 1, 2) if f.nhwc else f.t[:, :f.C]).detach().float().cpu().numpy()
+            for i, f in enumerate((fa, fb) if fb is not None else (fa,)):
+                c, n, m, _ = incr_ref(view(s, f.C), nchw(f))
+                counts[i] += torch.from_numpy(c)
+                finite[i] += torch.from_numpy(n)
+                moments[i] += torch.from_numpy(m)
+
+    return IncrEmuOps("f32")
+
+
+def _patch(setattr_):
+    from downgan_amd import backend
+    from downgan_amd.GAN import losses
+    setattr_(backend, "make_ops", lambda dtype, device: incr_emu_ops())
+    setattr_(losses, "_ops", {})
+    setattr_(increments, "_ops", {})
+
+
+HOOK_SPEC = IncrementSpec.zscore(2, lags=(1, 4, 127, 128), nbins=32)               # 128 x 128 tiles: lag 128 contributes nothing
+
+
+def _run_epoch(log_increments, dist=None, lo=0, step=1, batch=2, fs=False):
+    from downgan_amd.GAN.wasserstein import WassersteinGAN
+    from downgan_amd.GAN.wasserstein_fs import WassersteinGANFS
+    from downgan_amd.networks.critic import Critic
+    from downgan_amd.networks.generator import Generator
+    torch.manual_seed(0)                                  # initial weights, the gradient penalty's alpha
+    G, C_ = Generator(16, 128, 2, 2, num_res_blocks=1), Critic(16, 128, 2)
+    tr = (WassersteinGANFS if fs else WassersteinGAN)(G, C_, dist=dist)
+    tr.log_increments = log_increments
+    tr.increment_spec = HOOK_SPEC
+    dl, tl = _loaders(lo, step, batch)
+    tr.train(dl, tl, epochs=1)
+    return tr
+
+
+def _check_summary(p, fields):
+    assert {"channels", "lags", "fields", "grid", "real", "fake", "w1", "ks", "flatness_ratio"} <= set(p)
+    assert p["fields"] == fields and p["channels"] == ["ch0", "ch1", "speed"] and p["lags"] == [1, 4, 127, 128]
+    assert p["grid"] == [128, 128]
+    for side in ("real", "fake"):
+        assert np.array(p[side]["finite"]).tolist() == [[[fields * 128 * (128 - r) for r in (1, 4, 127, 128)]] * 2] * 3
+        fl = np.array(p[side]["flatness"], dtype=object)
+        assert fl.shape == (3, 2, 4) and all(v is None for v in fl[..., 3].reshape(-1)) and all(v > 1 for v in fl[..., :3].reshape(-1))
+        assert set(p[side]["longitudinal"]) == {"S2", "flatness"}
+    assert all(v is None for v in np.array(p["w1"], dtype=object)[..., 3].reshape(-1))
+    assert all(0 <= v <= 1 for v in np.array(p["ks"], dtype=object)[..., :3].reshape(-1))
+
+
+def test_log_increments_off_leaves_the_summary_unchanged(monkeypatch):
+    import downgan_amd.config.hyperparams as hp
+    _patch(monkeypatch.setattr)
+    monkeypatch.setattr(hp, "batch_size", 2)
+    torch.set_num_threads(4)
+    from downgan_amd.GAN.wasserstein import WassersteinGAN
+    assert WassersteinGAN.log_increments is False and WassersteinGAN.increment_spec is None
+    assert WassersteinGAN.increment_results is None
+    off = _run_epoch(False).metrics_log[0]
+    tr = _run_epoch(True)
+    on = dict(tr.metrics_log[0])
+    assert "increments" not in off
+    d = on.pop("increments")
+    assert json.dumps(on, sort_keys=True) == json.dumps(off, sort_keys=True)     # the hook adds a key and changes nothing else
+    json.dumps(d, allow_nan=False)
+    assert set(d) == {"train", "test"}
+    _check_summary(d["train"], 2)
+    _check_summary(d["test"], 4)
+    from downgan_amd import synthetic
+    coarse, fine = synthetic.tiles(6, 2, 16, seed=11)
+    res = tr.increment_results["test"]
+    assert res.fields == 4 and res.spec == HOOK_SPEC and res.nser == 2
+    with torch.no_grad():
+        fake = np.concatenate([tr.G(torch.from_numpy(coarse[a:a + 2])).float().numpy() for a in (2, 4)])
+    for i, x in enumerate((fine[2:6], fake)):
+        ref = spec_ref(HOOK_SPEC, x)
+        np.testing.assert_array_equal(res.counts[i], ref[0])
+        np.testing.assert_array_equal(res.finite[i], ref[1])
+        np.testing.assert_allclose(res.moments[i], ref[2], rtol=1e-11, atol=1e-9)   # two batches, each summed by fsum, then added
+    assert d["test"]["w1"] == increments._jsonable(res.w1())
+
+
+def test_log_increments_without_log_metrics_and_in_the_frequency_separation_trainer(monkeypatch):
+    import downgan_amd.config.hyperparams as hp
+    _patch(monkeypatch.setattr)
+    monkeypatch.setattr(hp, "batch_size", 2)
+    torch.set_num_threads(4)
+    s = _run_epoch(True, fs=True).metrics_log[0]
+    _check_summary(s["increments"]["train"], 2)
+    _check_summary(s["increments"]["test"], 4)
+    from downgan_amd.GAN.wasserstein import WassersteinGAN
+    monkeypatch.setattr(WassersteinGAN, "log_metrics", False)
+    s = _run_epoch(True).metrics_log[0]
+    assert "train" not in s and s["increments"]["train"]["fields"] == 2 and s["increments"]["test"]["fields"] == 4
+
+
+def _worker(rank, world, port, outdir):
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    torch.set_num_threads(2)
+    import downgan_amd.config.hyperparams as hp
+    _patch(setattr)
+    hp.batch_size, hp.lr = 1, 0.0
+    from downgan_amd.dist import Dist
+    d = Dist("gloo")
+    tr = _run_epoch(True, dist=d, lo=rank, step=world, batch=1)
+    torch.save({"summary": tr.metrics_log[0]["increments"],
+                "tables": {k: (v.counts, v.finite, v.moments, v.fields) for k, v in tr.increment_results.items()}},
+               os.path.join(outdir, f"r{rank}.pt"))
+    d.barrier()
+
+
+def test_two_gloo_ranks_give_the_single_process_tables(monkeypatch):
+    """lr = 0 keeps G identical in both runs, so the generated fields are the same and only the reduction is tested."""
+    import downgan_amd.config.hyperparams as hp
+    _patch(monkeypatch.setattr)
+    monkeypatch.setattr(hp, "batch_size", 2)
+    monkeypatch.setattr(hp, "lr", 0.0)
+    torch.set_num_threads(4)
+    tr = _run_epoch(True)
+    ref = tr.increment_results
+    with tempfile.TemporaryDirectory() as d:
+        from downgan_amd.dist import free_port
+        mp.spawn(_worker, args=(2, free_port(), d), nprocs=2, join=True)
+        r0, r1 = (torch.load(os.path.join(d, f"r{r}.pt"), weights_only=False) for r in range(2))
+    assert json.dumps(r0["summary"], sort_keys=True) == json.dumps(r1["summary"], sort_keys=True)
+    for part in ("train", "test"):
+        for r in (r0, r1):
+            c, n, m, fields = r["tables"][part]
+            np.testing.assert_array_equal(c, ref[part].counts)
+            np.testing.assert_array_equal(n, ref[part].finite)
+            np.testing.assert_allclose(m, ref[part].moments, rtol=1e-11, atol=1e-9)     # fp64 sums in another order
+            assert fields == ref[part].fields
