@@ -148,7 +148,7 @@ class WassersteinGAN:
         return float(e._sc("gp_ret").item())
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                                  coherence=None, increments=None):
+                                  coherence=None, increments=None, hist_maps=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
@@ -156,7 +156,8 @@ class WassersteinGAN:
         mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
         ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair;
         ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair; ``increments``: one ``increments.Increments`` fed the
-        same pair."""
+        same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given)."""
+        more = {} if hist_maps is None else {"hist_maps": hist_maps}
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -169,11 +170,11 @@ class WassersteinGAN:
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
             return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
-                                  coherence=coherence, increments=increments)
+                                  coherence=coherence, increments=increments, **more)
         e = self._eng(coarse, fine)
         xc, xf = self._to_native(e, coarse, fine)
         return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
-                              coherence=coherence, increments=increments)
+                              coherence=coherence, increments=increments, **more)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -218,6 +219,15 @@ class WassersteinGAN:
     log_increments = False
     increment_spec = None
     increment_results = None     # the last epoch's {"train" / "test": increments.IncrementResult} when logged
+    # opt-in: per-gridpoint histograms of the same (real, generated) pairs -- maps of the local quantiles (quantile_map_q), their
+    # bias and the local W1 / KS distances (an exact int32 table per pixel on the device: gridhist.GridHist.nbytes), their summary
+    # reported per epoch in summary["quantile_maps"]; quantile_map_spec None = histograms.HistSpec.zscore(n_predictands, bins=64,
+    # lim=6.0); quantile_map_dir: the maps are saved under <quantile_map_dir>/<epoch>/<part>/ as .npy files
+    log_quantile_maps = False
+    quantile_map_spec = None
+    quantile_map_q = (0.5, 0.95, 0.99)
+    quantile_map_dir = None
+    quantile_map_results = None  # the last epoch's {"train" / "test": gridhist.GridHistMaps} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -260,6 +270,13 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return Increments(spec, device=dev)
 
+    def _quantile_map_acc(self, fine):
+        from ..gridhist import GridHist
+        from ..histograms import HistSpec
+        spec = self.quantile_map_spec if self.quantile_map_spec is not None else HistSpec.zscore(self.G.n_predictands, bins=64, lim=6.0)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return GridHist(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
     def _coherence_acc(self, fine):
         from ..spectra import CrossSpectrum
         dev = self._engine.ops.device if self._engine is not None else self.G.device
@@ -267,7 +284,7 @@ class WassersteinGAN:
 
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -305,6 +322,11 @@ class WassersteinGAN:
             if part not in i:
                 i[part] = self._increment_acc()
             kw["increments"] = i[part]
+        if self.log_quantile_maps:
+            h = acc.setdefault("quantile_maps", {})
+            if part not in h:
+                h[part] = self._quantile_map_acc(fine)
+            kw["hist_maps"] = h[part]
         return kw
 
     def _coherence_summary(self, acc):
@@ -318,6 +340,17 @@ class WassersteinGAN:
         return {"real": s[:, 0].tolist(), "fake": s[:, 1].tolist(), "co": s[:, 2].tolist(), "coherence": coh.tolist(),
                 "rel_error": relative_error_spectrum(s).tolist(), "k_eff": [int(k) for k in k_eff],
                 "wavelength_px": [float(w) for w in wavelength_px(k_eff, acc.N)], "fields": acc.count}
+
+    def _quantile_map_summary(self, part, acc, epoch):
+        """The JSON-serialisable summary of one part's accumulator (the table summed exactly over the data-parallel ranks
+        first); the GridHistMaps is kept in ``quantile_map_results`` and, with ``quantile_map_dir``, saved by the first rank."""
+        res = acc.reduce_(self.dist).result()
+        self.quantile_map_results[part] = res
+        q = tuple(self.quantile_map_q)
+        if self.quantile_map_dir is not None and (self.dist is None or self.dist.rank == 0):
+            import os
+            res.save(os.path.join(self.quantile_map_dir, str(epoch), part), q)
+        return res.summary(q)
 
     def _increment_summary(self, part, acc):
         """The JSON-serialisable summary of one part's accumulator (counts summed exactly, moments in fp64, over the data-parallel
@@ -410,7 +443,7 @@ class WassersteinGAN:
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
         if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
-                or self.log_coherence or self.log_increments):
+                or self.log_coherence or self.log_increments or self.log_quantile_maps):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -433,6 +466,9 @@ class WassersteinGAN:
             if self.log_increments:
                 self.increment_results = {}
                 summary["increments"] = {k: self._increment_summary(k, v) for k, v in acc.get("increments", {}).items()}
+            if self.log_quantile_maps:
+                self.quantile_map_results = {}
+                summary["quantile_maps"] = {k: self._quantile_map_summary(k, v, epoch) for k, v in acc.get("quantile_maps", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

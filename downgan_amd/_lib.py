@@ -83,6 +83,7 @@ GRID_MAX_THR = 4
 FSS_MAX_THR, FSS_MAX_SCALES, FSS_MAX_SIDE = 4, 8, 2048
 HIST2D_MAX_PAIRS, HIST2D_MAX_CELLS, HIST2D_MAX_SECTORS = 8, 16384, 72
 INCR_MAX_LAGS, INCR_MAX_LAG, INCR_MAX_BINS, INCR_MAX_SIDE = 8, 256, 512, 2048
+GRIDHIST_MAX_BINS, GRIDHIST_MAX_Q = 256, 16
 
 
 class EofFields(C.Structure):
@@ -211,10 +212,15 @@ _PROTOS = {
     "dg_incr_ws_bytes": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(IncrSpec)],
     "dg_incr": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(IncrSpec), _vp, _vp, _vp, _vp, _vp],
     "dg_incr_host": [C.POINTER(IncrSpec), _vp, _i, _i, _i, _vp, _vp, _vp],
+    "dg_gridhist_ws_bytes": [C.POINTER(EofFields), _i, C.POINTER(HistSpec)],
+    "dg_gridhist": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(HistSpec), _vp, _vp, _vp],
+    "dg_gridhist_scan": [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _vp],
+    "dg_gridhist_host": [C.POINTER(HistSpec), _vp, _vp, _i, _i, _i, _vp],
+    "dg_gridhist_scan_host": [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp],
 }
 _RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
              "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t,
-             "dg_incr_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+             "dg_incr_ws_bytes": C.c_size_t, "dg_gridhist_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

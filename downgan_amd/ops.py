@@ -976,6 +976,44 @@ class HipOps:
         check(self.lib.dg_gridstats(C.byref(fa), C.byref(fb) if paired else None, C.byref(spec), _ptr(ws), _ptr(sums),
                                     _ptr(extrema), _ptr(counts), self._stream()), "dg_gridstats")
 
+    # ------------------------------------------------------------------ per-gridpoint histograms (csrc/gridhist.hip)
+    def gridhist_ws_bytes(self, f, paired, spec):
+        """Workspace bytes of one dg_gridhist call over the descriptor ``f`` (one series, or with ``paired`` two) with the
+        _lib.HistSpec ``spec`` (0: invalid, e.g. more than _lib.GRIDHIST_MAX_BINS bins)."""
+        return int(self.lib.dg_gridhist_ws_bytes(C.byref(f), 1 if paired else 0, C.byref(spec)))
+
+    def gridhist(self, fa, fb, spec, counts):
+        """Accumulate the per-pixel histograms of the fields of ``fa`` (eof_fields; with ``fb`` not None: of the pair fa, fb)
+        under ``spec`` (_lib.HistSpec): counts int32 [nout, 1 | 2, nbins + 3, P] += (rows: include/downgan_hip.h).  The
+        workspace is cached on this object."""
+        paired = fb is not None
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        n = nout * (2 if paired else 1) * (spec.nbins + 3) * fa.P
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == n and counts.is_cuda, (counts.dtype, counts.shape, n)
+        assert not paired or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.gridhist_ws_bytes(fa, paired, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, spec.nbins)
+        ws = getattr(self, "_gridhist_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._gridhist_ws = ws = None
+            self._gridhist_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_gridhist(C.byref(fa), C.byref(fb) if paired else None, C.byref(spec), _ptr(ws), _ptr(counts),
+                                   self._stream()), "dg_gridhist")
+
+    def gridhist_scan(self, counts, q, ranks, dist=None):
+        """Scan a per-pixel histogram table counts int32 [nout, S, nbins + 3, P] for the probabilities ``q`` (a sequence of
+        floats in (0, 1)): ranks int32 [nout, S, Q, 3, P] (row, count below it, count in it; -1, 0, 0 for an empty pixel) and,
+        for S = 2, dist int64 [nout, 2, P] (the integer W1 and KS sums) are overwritten."""
+        nout, S, nb3, P = counts.shape
+        Q = len(q)
+        assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.is_cuda, (counts.dtype, counts.shape)
+        assert ranks.dtype == torch.int32 and ranks.is_contiguous() and ranks.is_cuda and tuple(ranks.shape) == (nout, S, Q, 3, P), ranks.shape
+        assert (dist is None) == (S == 1), (S, dist is None)
+        assert dist is None or (dist.dtype == torch.int64 and dist.is_contiguous() and dist.is_cuda and tuple(dist.shape) == (nout, 2, P))
+        qa = (C.c_double * Q)(*[float(v) for v in q])
+        check(self.lib.dg_gridhist_scan(_ptr(counts), nout, S, nb3 - 3, P, qa, Q, _ptr(ranks), _ptr(dist), self._stream()),
+              "dg_gridhist_scan")
+
     # ------------------------------------------------------------------ fractions skill score (csrc/fss.hip)
     def fss_ws_bytes(self, f, H, W, spec):
         """Workspace bytes of one dg_fss call over the descriptor ``f`` (either series) of H x W fields with the _lib.FssSpec

@@ -767,6 +767,54 @@ int dg_incr(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const 
             int64_t* counts, int64_t* finite, double* moments, void* stream);
 int dg_incr_host(const dg_incr_spec* s, const float* x, int C, int H, int W, int64_t* counts, int64_t* finite, double* moments);
 
+/* ---- Per-gridpoint histograms (csrc/gridhist.hip) ---------------------------------------------------------------------------
+ * The distribution AT a gridpoint: one histogram per pixel and output channel over the fields t, from which follow the maps of
+ * local quantiles (P95 / P98 / P99 of wind speed, real against generated), the local QQ line and the local Wasserstein and
+ * Kolmogorov-Smirnov distances; the tables are also the input of empirical quantile mapping.  One series a, or two series a
+ * (real) and b (generated) of equal T, C, P, each read in place through the EOF descriptor (NCHW fp32 / bf16, the resident
+ * feed's [n, H, W, c] store, the generator's padded NHWC output; a and b may differ in layout and dtype).  The spec is the
+ * dg_hist_spec of the value histograms, and the output values y and their rows are those of dg_hist bit for bit (hist_affine,
+ * hist_speed, hist_bin of csrc/hist_common.h): row 0 underflow, 1 .. nbins interior, nbins + 1 overflow, nbins + 2 NaN.  The only
+ * new limit is nbins <= DG_GRIDHIST_MAX_BINS, because the table is per pixel:
+ *   counts  int32 [nout][S][nbins + 3][P]     S = 1 (b NULL) or 2 (real, generated); the pixel index fastest
+ *   counts[j][s][r][p] += #{t : output channel j of series s at pixel p falls in row r}
+ * nout * S * (nbins + 3) * P * 4 bytes: 1.6 GB for nout = 3, S = 2, nbins = 64 on a 1024^2 grid, 26 MB on 128^2.  dg_gridhist
+ * ACCUMULATES (the caller zeroes the table and keeps every count below 2^31).  A thread owns its pixels (four consecutive ones
+ * of an NCHW plane per 16 / 8-byte load, else one), a wave's pixels are contiguous, and the fields are cut into slices over
+ * the workgroups when P alone does not fill the chip; a thread walks its fields in t order, combines a run of equal rows in
+ * registers and adds it with one no-return 32-bit integer atomic at agent scope.  Integer adds commute: the counts are exact,
+ * do not depend on how the fields were chunked into calls, on layout or on dtype (bf16 inputs are the values read), and two
+ * calls on the same data are bit-identical.  No float atomics, no partial tables.
+ *
+ * dg_gridhist_scan reads a table and Q probabilities q_k (HOST pointer, fp64, 0 < q_k < 1, 1 <= Q <= DG_GRIDHIST_MAX_Q) and writes
+ * integers only.  Per (j, s, p), with n = the sum of rows 0 .. nbins + 1 (the finite values):
+ *   m = fp64(q_k * fp64(n)) (one rounded product);  k = (int64)ceil(m);  b = the first row whose cumulative count is >= k
+ *   ranks  int32 [nout][S][Q][3][P] = (b, cumulative count below row b, counts[b]);  (-1, 0, 0) for n = 0
+ * (n >= 1 and 0 < q < 1 give 1 <= k <= n, so counts[b] >= 1).  With S = 2, A_r / B_r the cumulative counts of a / b through row
+ * r and na / nb their finite totals:
+ *   dist   int64 [nout][2][P]
+ *   dist[j][0][p] = sum_{r = 0 .. nbins} g_r |A_r nb - B_r na|,  g_0 = g_nbins = 1, every other g_r = 2
+ *   dist[j][1][p] = max_{r = 0 .. nbins + 1} |A_r nb - B_r na|
+ * both -1 where na = 0 or nb = 0.  The host derives W1 = (w / 2) dist0 / (na nb) and KS = dist1 / (na nb): underflow mass at lo,
+ * interior bin at its centre, overflow at hi.  2 (nbins + 1) n^2 must stay below 2^63: the caller keeps n < 2^26.  One lane per
+ * pixel (per four pixels where P % 4 == 0) walks the rows twice (totals, then cumulative counts), plane-wise and coalesced; no
+ * atomics, no LDS, trip counts depend on nbins and Q only.
+ *
+ * dg_gridhist_ws_bytes: workspace bytes of one dg_gridhist call (0 for an invalid descriptor or spec; `paired` != 0: two series).
+ * dg_gridhist: b NULL = one series; ws may be NULL (the atomics need no partial state).
+ * dg_gridhist_scan: dist NULL when S = 1 (required when S = 2).
+ * dg_gridhist_host / dg_gridhist_scan_host: host-side, the same definitions in plain C++: xa, xb planar fp32 [T][C][P] (xb NULL:
+ *   one series), counts += as above; the scan with the same arguments on host arrays. */
+#define DG_GRIDHIST_MAX_BINS 256
+#define DG_GRIDHIST_MAX_Q 16
+size_t dg_gridhist_ws_bytes(const dg_eof_fields* a, int paired, const dg_hist_spec* s);
+int dg_gridhist(const dg_eof_fields* a, const dg_eof_fields* b, const dg_hist_spec* s, void* ws, int32_t* counts, void* stream);
+int dg_gridhist_scan(const int32_t* counts, int nout, int S, int nbins, int P, const double* q, int Q, int32_t* ranks,
+                     int64_t* dist, void* stream);
+int dg_gridhist_host(const dg_hist_spec* s, const float* xa, const float* xb, int C, int T, int P, int32_t* counts);
+int dg_gridhist_scan_host(const int32_t* counts, int nout, int S, int nbins, int P, const double* q, int Q, int32_t* ranks,
+                          int64_t* dist);
+
 #ifdef __cplusplus
 }
 #endif
