@@ -148,7 +148,7 @@ class WassersteinGAN:
         return float(e._sc("gp_ret").item())
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                                  coherence=None, increments=None, hist_maps=None):
+                                  coherence=None, increments=None, hist_maps=None, temporal=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
@@ -156,8 +156,11 @@ class WassersteinGAN:
         mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
         ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair;
         ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair; ``increments``: one ``increments.Increments`` fed the
-        same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given)."""
+        same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given); ``temporal``: one
+        paired ``temporal.Temporal`` fed the same pair as the next times of its series (likewise only when given)."""
         more = {} if hist_maps is None else {"hist_maps": hist_maps}
+        if temporal is not None:
+            more["temporal"] = temporal
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -228,6 +231,16 @@ class WassersteinGAN:
     quantile_map_q = (0.5, 0.95, 0.99)
     quantile_map_dir = None
     quantile_map_results = None  # the last epoch's {"train" / "test": gridhist.GridHistMaps} when logged
+    # opt-in: temporal diagnostics of the (real, generated) pairs of the TEST part only -- spell durations per threshold, ramp
+    # histograms per lead time and lag-autocorrelation maps, real against generated (what shows a generator that flickers from
+    # frame to frame), reported per epoch in summary["temporal"]; temporal_spec None = temporal.TemporalSpec.zscore(n_predictands);
+    # temporal_dir: saved under <temporal_dir>/<epoch>/test/.  The test loader MUST iterate in time order without shuffling: its
+    # batches are taken as consecutive times of one series.  Not available under data parallelism (the ranks hold interleaved
+    # samples, and a time series cannot be summed over them): world > 1 raises ValueError at the start of the epoch.
+    log_temporal = False
+    temporal_spec = None
+    temporal_dir = None
+    temporal_results = None      # the last epoch's {"test": temporal.TemporalResult} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -277,6 +290,12 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return GridHist(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
 
+    def _temporal_acc(self, fine):
+        from ..temporal import Temporal, TemporalSpec
+        spec = self.temporal_spec if self.temporal_spec is not None else TemporalSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return Temporal(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
     def _coherence_acc(self, fine):
         from ..spectra import CrossSpectrum
         dev = self._engine.ops.device if self._engine is not None else self.G.device
@@ -284,7 +303,7 @@ class WassersteinGAN:
 
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -327,6 +346,11 @@ class WassersteinGAN:
             if part not in h:
                 h[part] = self._quantile_map_acc(fine)
             kw["hist_maps"] = h[part]
+        if self.log_temporal and part == "test":                 # the test part only: the train batches are shuffled samples
+            t = acc.setdefault("temporal", {})
+            if part not in t:
+                t[part] = self._temporal_acc(fine)
+            kw["temporal"] = t[part]
         return kw
 
     def _coherence_summary(self, acc):
@@ -340,6 +364,16 @@ class WassersteinGAN:
         return {"real": s[:, 0].tolist(), "fake": s[:, 1].tolist(), "co": s[:, 2].tolist(), "coherence": coh.tolist(),
                 "rel_error": relative_error_spectrum(s).tolist(), "k_eff": [int(k) for k in k_eff],
                 "wavelength_px": [float(w) for w in wavelength_px(k_eff, acc.N)], "fields": acc.count}
+
+    def _temporal_summary(self, part, acc, epoch):
+        """The JSON-serialisable summary of the test part's accumulator (one rank: there is nothing to reduce); the
+        TemporalResult is kept in ``temporal_results`` and, with ``temporal_dir``, saved."""
+        res = acc.result()
+        self.temporal_results[part] = res
+        if self.temporal_dir is not None:
+            import os
+            res.save(os.path.join(self.temporal_dir, str(epoch), part))
+        return res.summary()
 
     def _quantile_map_summary(self, part, acc, epoch):
         """The JSON-serialisable summary of one part's accumulator (the table summed exactly over the data-parallel ranks
@@ -411,6 +445,9 @@ class WassersteinGAN:
         (same batch), metrics pass (:140-146); then the epoch means of the train metrics, the metrics over the test loader
         (:157-170) and the checkpoint (:178).  Plotting (gen_grid_images) and mlflow are out of scope; the per-step scalars are
         returned and the epoch summary is appended to ``self.metrics_log``."""
+        if self.log_temporal and self.dist is not None and self.dist.world_size > 1:
+            raise ValueError("log_temporal needs one rank: under data parallelism the ranks hold interleaved samples of the test "
+                             f"series, and a time series cannot be summed over them (world size {self.dist.world_size})")
         log, train_metrics, test_metrics = [], [], []
         acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" / "joint" / "coherence" -> {"train" / "test": accumulators}
         for data in dataloader:
@@ -443,7 +480,7 @@ class WassersteinGAN:
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
         if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
-                or self.log_coherence or self.log_increments or self.log_quantile_maps):
+                or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -469,6 +506,9 @@ class WassersteinGAN:
             if self.log_quantile_maps:
                 self.quantile_map_results = {}
                 summary["quantile_maps"] = {k: self._quantile_map_summary(k, v, epoch) for k, v in acc.get("quantile_maps", {}).items()}
+            if self.log_temporal:
+                self.temporal_results = {}
+                summary["temporal"] = {k: self._temporal_summary(k, v, epoch) for k, v in acc.get("temporal", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

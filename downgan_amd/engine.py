@@ -1237,7 +1237,7 @@ class TrainEngine:
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
     def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                     coherence=None, increments=None, hist_maps=None):
+                     coherence=None, increments=None, hist_maps=None, temporal=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1261,7 +1261,9 @@ class TrainEngine:
         ``coherence``: a ``spectra.CrossSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the cross spectra
         of the pair (per-scale coherence, error spectrum, effective resolution).
         ``hist_maps``: a paired ``gridhist.GridHist`` that likewise receives (fine[:n], fake[:n]) in one call: the per-gridpoint
-        histograms of both series (local quantiles, W1 / KS per pixel)."""
+        histograms of both series (local quantiles, W1 / KS per pixel).
+        ``temporal``: a paired ``temporal.Temporal`` that likewise receives (fine[:n], fake[:n]) in one call, as the next n times
+        of its series: the caller feeds the batches in time order."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1288,6 +1290,8 @@ class TrainEngine:
             increments.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if hist_maps is not None:
             hist_maps.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if temporal is not None:
+            temporal.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

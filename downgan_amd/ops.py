@@ -1014,6 +1014,37 @@ class HipOps:
         check(self.lib.dg_gridhist_scan(_ptr(counts), nout, S, nb3 - 3, P, qa, Q, _ptr(ranks), _ptr(dist), self._stream()),
               "dg_gridhist_scan")
 
+    # ------------------------------------------------------------------ temporal diagnostics (csrc/temporal.hip)
+    def temporal_ws_bytes(self, fa, fb, spec):
+        """Workspace bytes of one dg_temporal call over the descriptors ``fa`` (and ``fb``, or None) with the _lib.TemporalSpec
+        ``spec`` (0: invalid)."""
+        return int(self.lib.dg_temporal_ws_bytes(C.byref(fa), C.byref(fb) if fb is not None else None, C.byref(spec)))
+
+    def temporal(self, fa, fb, spec, t0, open_, tail, spells, spellmap, ramps, acsum, accnt):
+        """Add the fields of ``fa`` (eof_fields, in time order; ``fb``: the second series, or None) as the times t0 .. t0 + T - 1
+        under ``spec`` (_lib.TemporalSpec), S = 2 with ``fb``: open_ int32 [S, nout, nthr, P] and tail fp32 [S, nout, R, P] are
+        the carried state, spells int64 [S, nout, nthr, ndur] +=, spellmap int32 [S, nout, nthr, 3, P], ramps int64
+        [S, nout, nlag, nbins + 3] +=, acsum fp64 [S, nout, 2 + 2 nlag, P], accnt int32 [S, nout, 1 + nlag, P] (rows:
+        include/downgan_hip.h).  Arrays that the spec leaves empty (nthr = 0: open_, spells, spellmap; nlag = 0: tail, ramps)
+        may be None."""
+        S = 2 if fb is not None else 1
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        nthr, nlag, P = spec.nthr, spec.nlag, fa.P
+        R = spec.lag[nlag - 1] if nlag else 0
+        for out, dt, n in ((open_, torch.int32, nthr * P), (tail, torch.float32, R * P), (spells, torch.int64, nthr * spec.ndur),
+                           (spellmap, torch.int32, nthr * 3 * P), (ramps, torch.int64, nlag * (spec.nbins + 3)),
+                           (acsum, torch.float64, (2 + 2 * nlag) * P), (accnt, torch.int32, (1 + nlag) * P)):
+            if out is None or n == 0:
+                assert n == 0, "an array the spec needs is missing"
+                continue
+            assert out.dtype == dt and out.is_contiguous() and out.numel() == S * nout * n and out.is_cuda, (out.dtype, out.shape, S * nout * n)
+        assert fb is None or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        assert self.temporal_ws_bytes(fa, fb, spec) > 0, (fa.T, fa.C, fa.P, nthr, nlag)
+        ptr = lambda t: _ptr(t) if t is not None and t.numel() else None
+        check(self.lib.dg_temporal(C.byref(fa), C.byref(fb) if fb is not None else None, C.byref(spec), int(t0), None, ptr(open_),
+                                   ptr(tail), ptr(spells), ptr(spellmap), ptr(ramps), ptr(acsum), ptr(accnt), self._stream()),
+              "dg_temporal")
+
     # ------------------------------------------------------------------ fractions skill score (csrc/fss.hip)
     def fss_ws_bytes(self, f, H, W, spec):
         """Workspace bytes of one dg_fss call over the descriptor ``f`` (either series) of H x W fields with the _lib.FssSpec

@@ -815,6 +815,79 @@ int dg_gridhist_host(const dg_hist_spec* s, const float* xa, const float* xb, in
 int dg_gridhist_scan_host(const int32_t* counts, int nout, int S, int nbins, int P, const double* q, int Q, int32_t* ranks,
                           int64_t* dist);
 
+/* ---- Temporal diagnostics (csrc/temporal.hip) -------------------------------------------------------------------------------
+ * Every other diagnostic treats the fields of a series as an unordered sample; this one looks along the time axis of one series:
+ * how long a gridpoint stays above / below a threshold (spell durations), how fast it changes (ramps y(t) - y(t - tau)) and how
+ * persistent it is (lag autocorrelation).  A SERIES is a sequence of fields in time order.  Series a (real) is required, series b
+ * (generated) is optional, of equal T, C, P, each read in place through the EOF descriptor (NCHW fp32 / bf16, the resident feed's
+ * [n, H, W, c] store, the generator's padded NHWC output; a and b may differ in layout and dtype).  S = 1 (b NULL) or 2.  The
+ * output values y are those of the value histograms bit for bit (hist_affine, hist_speed of csrc/hist_common.h, the speed
+ * appended as output channel C: nout = C + 1 with speed_u >= 0, else C).
+ * Time is absolute: a call carries t0, the number of fields added before it, and its fields are the times t0 .. t0 + T - 1.
+ * Everything below ACCUMULATES into caller-owned device arrays (zeroed by the caller before the first call); the pixel index is
+ * fastest wherever P appears.
+ *
+ * Spells.  Condition k of output channel j: y > thr[j][k] (below[k] = 0) or y < thr[j][k] (below[k] = 1), fp32 compares: false
+ * for NaN and for equality.  A spell of (s, j, k, p) is a maximal run of consecutive times at which the condition holds; it
+ * completes at the first time at which the condition fails.
+ *   open     int32 [S][nout][nthr][P]       the length of the run still open after the last field added (carried state)
+ *   spells   int64 [S][nout][nthr][ndur]    spells[..][min(len, ndur) - 1] += 1 per completed spell, pooled over the pixels
+ *   spellmap int32 [S][nout][nthr][3][P]    row 0: completed spells; row 1: the total time in completed spells; row 2: the
+ *                                           longest run seen, open runs included
+ * A run still open after the last field is in no row of spells (it is right-censored; the caller reads it from open).  A run that
+ * starts at time 0 is counted like any other although its true start is unknown: it is LEFT-CENSORED.
+ *
+ * Ramps.  For tau = lag[l] and t - tau >= 0: d = hist_diff(y[t], y[t - tau]), one rounded fp32 subtraction of the rounded y.
+ *   ramps    int64 [S][nout][nlag][nbins + 3]   ramps[..][hist_bin(d, lo[j][l], inv_w[j][l], nbins)] += 1, pooled over the pixels
+ * with the rows of dg_hist (0 underflow, 1 .. nbins interior, nbins + 1 overflow, nbins + 2 NaN: a NaN operand, or inf - inf).
+ *
+ * Persistence.  Per (s, j, p), never contracted, every sum in fp64 added in t order:
+ *   accnt    int32 [S][nout][1 + nlag][P]       row 0: n = #{t : y[t] finite};  row 1 + l: m_l = #{t : y[t], y[t - tau_l] finite}
+ *   acsum    fp64  [S][nout][2 + 2 nlag][P]     row 0: s1 = sum (double)y;  row 1: s2 = sum (double)y * (double)y  (finite y);
+ *                                               row 2 + 2l: c_l = sum (double)y[t] * (double)y[t - tau_l]  (the product of two
+ *                                               fp32 is exact in fp64);  row 3 + 2l: e_l = sum ((double)y[t] + (double)y[t - tau_l])
+ *                                               (both over the t counted by m_l)
+ *   tail     fp32  [S][nout][R][P], R = lag[nlag - 1]: tail[..][t mod R] = y at time t for the last R times (carried state;
+ *                                               absent -- may be NULL -- when nlag = 0)
+ * The host derives mu = s1 / n and r_l = (c_l / m_l - mu e_l / m_l + mu^2) / (s2 / n - mu^2).
+ *
+ * The chunking contract: every output, the bits of the fp64 sums and the carried state included, is the same however the series
+ * was cut into calls (calls of one field and calls shorter than the largest lag included), and does not depend on layout or
+ * dtype (bf16 inputs are the values read); two runs on the same data are bit-identical.  The fields of a call are therefore NOT
+ * cut into time slices: a thread owns its pixels (four consecutive ones of an NCHW plane per 16 / 8-byte load on large grids,
+ * else one) of one output channel of one series and walks the call's fields in t order with its open runs, counts and fp64 sums
+ * in registers; y[t - tau] is recomputed from field t - tau of the same call (a second read, served by the caches) or, for
+ * t - tau < t0, taken from tail.  The pooled tables go through uint32 LDS tables flushed with 64-bit integer atomics.  Integer
+ * atomics only, no float atomics, no loop whose trip count depends on data.
+ *
+ * dg_temporal_ws_bytes: workspace bytes of one call (0 for an invalid call, else a small non-zero value: no workspace is needed).
+ * dg_temporal: ws may be NULL.  open, spells, spellmap may be NULL when nthr = 0; tail, ramps when nlag = 0.  Rejected before any
+ *   launch (DG_ERR_BAD_SHAPE; DG_ERR_BAD_DTYPE for a dtype other than fp32 / bf16): a NULL pointer that is needed, series that
+ *   differ in T, C or P, nthr, ndur, nlag or nbins out of range, nthr = nlag = 0, a below that is not 0 or 1, lags unsorted or
+ *   out of range, a non-finite thr, lo, inv_w, scale or offset, inv_w <= 0, speed channels that do not exist, t0 < 0,
+ *   t0 + T >= 2^31.
+ * dg_temporal_host: host-side, the same definition in plain C++ for ONE series, planar fp32 [T][C][P], with the same t0 and the
+ *   state and output arrays of one series (the [S] dimension dropped). */
+#define DG_TEMPORAL_MAX_THR 4
+#define DG_TEMPORAL_MAX_DUR 256
+#define DG_TEMPORAL_MAX_LAGS 4
+#define DG_TEMPORAL_MAX_LAG 24
+#define DG_TEMPORAL_MAX_BINS 512
+typedef struct dg_temporal_spec {
+  int speed_u, speed_v;                    /* input channels of the speed channel, or -1, -1: none */
+  int nthr, ndur, nlag, nbins;             /* 0 .. MAX_THR, 1 .. MAX_DUR, 0 .. MAX_LAGS, 1 .. MAX_BINS; nthr + nlag >= 1 */
+  int below[DG_TEMPORAL_MAX_THR];          /* 0: y > thr; 1: y < thr */
+  int lag[DG_TEMPORAL_MAX_LAGS];           /* 1 <= lag <= DG_TEMPORAL_MAX_LAG, strictly increasing */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];                   /* per input channel, finite */
+  float thr[DG_HIST_MAX_OUT][DG_TEMPORAL_MAX_THR];                   /* finite */
+  float lo[DG_HIST_MAX_OUT][DG_TEMPORAL_MAX_LAGS], inv_w[DG_HIST_MAX_OUT][DG_TEMPORAL_MAX_LAGS];   /* finite; inv_w > 0 */
+} dg_temporal_spec;
+size_t dg_temporal_ws_bytes(const dg_eof_fields* a, const dg_eof_fields* b, const dg_temporal_spec* s);
+int dg_temporal(const dg_eof_fields* a, const dg_eof_fields* b, const dg_temporal_spec* s, int64_t t0, void* ws, int32_t* open,
+                float* tail, int64_t* spells, int32_t* spellmap, int64_t* ramps, double* acsum, int32_t* accnt, void* stream);
+int dg_temporal_host(const dg_temporal_spec* s, const float* x, int C, int T, int P, int64_t t0, int32_t* open, float* tail,
+                     int64_t* spells, int32_t* spellmap, int64_t* ramps, double* acsum, int32_t* accnt);
+
 #ifdef __cplusplus
 }
 #endif
