@@ -148,7 +148,7 @@ class WassersteinGAN:
         return float(e._sc("gp_ret").item())
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                                  coherence=None, increments=None, hist_maps=None, temporal=None):
+                                  coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
@@ -157,10 +157,13 @@ class WassersteinGAN:
         ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair;
         ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair; ``increments``: one ``increments.Increments`` fed the
         same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given); ``temporal``: one
-        paired ``temporal.Temporal`` fed the same pair as the next times of its series (likewise only when given)."""
+        paired ``temporal.Temporal`` fed the same pair as the next times of its series (likewise only when given); ``helmholtz``:
+        one ``spectra.HelmholtzSpectrum`` fed the same pair (likewise only when given)."""
         more = {} if hist_maps is None else {"hist_maps": hist_maps}
         if temporal is not None:
             more["temporal"] = temporal
+        if helmholtz is not None:
+            more["helmholtz"] = helmholtz
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -241,6 +244,16 @@ class WassersteinGAN:
     temporal_spec = None
     temporal_dir = None
     temporal_results = None      # the last epoch's {"test": temporal.TemporalResult} when logged
+    # opt-in: Helmholtz spectra of the same (real, generated) pairs -- the kinetic energy spectrum of the wind (channels
+    # helmholtz_pair = (u, v)) split into its rotational and divergent parts, the divergent fraction per scale and the coherence
+    # and effective resolution (at helmholtz_threshold) of each part, reported per epoch in summary["helmholtz"].  helmholtz_scale
+    # (su, sv): on z-scored channels pass their standard deviations, the split is not invariant under per-channel scaling;
+    # helmholtz_rows_up False: the rows run north to south.  Needs n_predictands >= 2 (ValueError at the start of the epoch)
+    log_helmholtz = False
+    helmholtz_pair = (0, 1)
+    helmholtz_scale = None
+    helmholtz_rows_up = True
+    helmholtz_threshold = 0.5
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -301,9 +314,15 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return CrossSpectrum(self.G.n_predictands, fine.shape[-1], device=dev)
 
+    def _helmholtz_acc(self, fine):
+        from ..spectra import HelmholtzSpectrum
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return HelmholtzSpectrum(fine.shape[-1], pair=self.helmholtz_pair, scale=self.helmholtz_scale,
+                                 rows_up=self.helmholtz_rows_up, device=dev)
+
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}, "helmholtz": {part: HelmholtzSpectrum}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -351,7 +370,29 @@ class WassersteinGAN:
             if part not in t:
                 t[part] = self._temporal_acc(fine)
             kw["temporal"] = t[part]
+        if self.log_helmholtz:
+            z = acc.setdefault("helmholtz", {})
+            if part not in z:
+                z[part] = self._helmholtz_acc(fine)
+            kw["helmholtz"] = z[part]
         return kw
+
+    def _helmholtz_summary(self, acc):
+        """The eight mean planes by name ([K] each), "div_frac_real", "div_frac_fake" (div / (rot + div), NaN on ring 0),
+        "coh_rot", "coh_div": [K], "k_eff_rot", "k_eff_div" (effective resolution of each part at ``helmholtz_threshold``),
+        "wavelength_px_rot", "wavelength_px_div" and "fields" of one part's accumulator, summed over the data-parallel ranks
+        first."""
+        from ..spectra import (HELM_CROSS_PLANES, divergent_fraction, effective_resolution, helmholtz_coherence, wavelength_px)
+        s = acc.reduce_(self.dist).mean().cpu().numpy()
+        frac, coh = divergent_fraction(s), helmholtz_coherence(s)
+        out = {name: s[i].tolist() for i, name in enumerate(HELM_CROSS_PLANES)}
+        out.update(div_frac_real=frac[0].tolist(), div_frac_fake=frac[1].tolist(), coh_rot=coh[0].tolist(), coh_div=coh[1].tolist())
+        for i, what in enumerate(("rot", "div")):
+            k = effective_resolution(coh[i], self.helmholtz_threshold)
+            out["k_eff_" + what] = int(k)
+            out["wavelength_px_" + what] = float(wavelength_px(k, acc.N))
+        out["fields"] = acc.count
+        return out
 
     def _coherence_summary(self, acc):
         """{"real", "fake", "co": [C][K] mean spectra of the real and generated fields and their co-spectrum, "coherence",
@@ -448,6 +489,12 @@ class WassersteinGAN:
         if self.log_temporal and self.dist is not None and self.dist.world_size > 1:
             raise ValueError("log_temporal needs one rank: under data parallelism the ranks hold interleaved samples of the test "
                              f"series, and a time series cannot be summed over them (world size {self.dist.world_size})")
+        if self.log_helmholtz:
+            from ..spectra import _helm_pair, _helm_scale
+            if self.G.n_predictands < 2:
+                raise ValueError(f"log_helmholtz needs a wind field: n_predictands >= 2 (got {self.G.n_predictands})")
+            _helm_pair(self.helmholtz_pair, self.G.n_predictands)
+            _helm_scale(self.helmholtz_scale, self.helmholtz_rows_up)
         log, train_metrics, test_metrics = [], [], []
         acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" / "joint" / "coherence" -> {"train" / "test": accumulators}
         for data in dataloader:
@@ -480,7 +527,7 @@ class WassersteinGAN:
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
         if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
-                or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal):
+                or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal or self.log_helmholtz):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -509,6 +556,8 @@ class WassersteinGAN:
             if self.log_temporal:
                 self.temporal_results = {}
                 summary["temporal"] = {k: self._temporal_summary(k, v, epoch) for k, v in acc.get("temporal", {}).items()}
+            if self.log_helmholtz:
+                summary["helmholtz"] = {k: self._helmholtz_summary(v) for k, v in acc.get("helmholtz", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

@@ -205,6 +205,10 @@ _PROTOS = {
     "dg_rapsd_ring_counts": [_i, C.POINTER(_i64)],
     "dg_cross_rapsd_ws_bytes": [_i, _i, _i],
     "dg_cross_rapsd": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _vp, _vp, _vp, _vp],
+    "dg_helmholtz_ws_bytes": [_i, _i],
+    "dg_helmholtz": [C.POINTER(EofFields), _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp, _vp],
+    "dg_helmholtz_cross_ws_bytes": [_i, _i],
+    "dg_helmholtz_cross": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(_f), _i, _vp, _vp, _vp, _vp],
     "dg_hist_ws_bytes": [C.POINTER(EofFields), C.POINTER(HistSpec)],
     "dg_hist": [C.POINTER(EofFields), C.POINTER(HistSpec), _vp, _vp, _vp, _vp, _vp],
     "dg_hist_host_bins": [C.POINTER(HistSpec), _vp, _i, _i64, _vp],
@@ -231,7 +235,8 @@ _PROTOS = {
                     _vp],
     "dg_temporal_host": [C.POINTER(TemporalSpec), _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
 }
-_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
+_RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_size_t,
+             "dg_helmholtz_ws_bytes": C.c_size_t, "dg_helmholtz_cross_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
              "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t,
              "dg_incr_ws_bytes": C.c_size_t, "dg_gridhist_ws_bytes": C.c_size_t,
              "dg_temporal_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status

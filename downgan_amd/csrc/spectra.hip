@@ -22,6 +22,26 @@
 //                          workgroups (8 waves) share a CU's 160 KB; rapsd_col_kernel's 48 KB would admit three.
 //   cross_field_kernel     slices summed in order, divided by the ring counts -> per-field [3][K]
 //   cross_sum_kernel       sum[c][plane][k] over t, in t order
+//
+// Helmholtz spectra (include/downgan_hip.h "Helmholtz spectra") of a vector field (u, v), U = su FFT2(u), V = sv FFT2(v): ring
+// means of ke = (|U|^2 + |V|^2) / (2 N^2), rot = |kx V - ky U|^2 / (2 k2 N^2) and div = |kx U + ky V|^2 / (2 k2 N^2), kx the
+// signed wavenumber along W (the line index u of the half spectra), ky along H, k2 = kx^2 + ky^2 (rot = div = 0 at k2 = 0); for
+// a pair of vector fields also co_rot = Re(Ra conj Rb) / (2 k2 N^2) and co_div likewise, R = kx V - ky U, D = kx U + ky V.
+//   rapsd_row_kernel       unchanged, once per component and side through a one-channel descriptor
+//   helm_col_kernel        per slice of lines: helm_side (FFT of U^'s lines, parked in the third LDS buffer, FFT of V^'s lines,
+//                          then per point in fp32 the scaled U, V and ke, rot, div with the Hermitian weight), the three planes
+//                          ring-summed in fp64 with rapsd_col_kernel's slices and loop order.  LDS 64 KB as cross_col_kernel.
+//   helm_cross_col_kernel  side a as above; its U, V stay in registers while side b runs through the same buffers; then side
+//                          b's planes and the two co-planes.  Both kernels call the same helm_side and the same per-plane ring
+//                          sums, so planes 0-5 equal the one-sided calls on a and on b bit for bit, and (a, a) gives
+//                          co_rot = rot, co_div = div bit for bit.
+//   helm_field_kernel, helm_sum_kernel   cross_field_kernel / cross_sum_kernel for 3 or 8 planes of one field per time
+// NYQUIST RULE.  The half spectrum holds each conjugate pair once with weight 2.  At v = N/2 on a line 0 < u < N/2 the two
+// members are (kx, -N/2) and (-kx, -N/2) in fftfreq's convention, and on the line u = N/2 the members (-N/2, v), (-N/2, -v) lie
+// in one ring: in both cases the cross term 2 kx ky Re(U conj V) of |D|^2 and |R|^2 has opposite signs for the two and cancels
+// in the ring sum.  So every point with u = N/2 or v = N/2 contributes WITHOUT the cross term,
+//   div ~ kx^2 |U|^2 + ky^2 |V|^2,  rot ~ kx^2 |V|^2 + ky^2 |U|^2   (co-planes: the corresponding real parts),
+// which for real inputs equals the full-spectrum definition exactly (the corner (N/2, N/2) lies outside the last ring).
 #include "dg_internal.h"
 
 namespace {
@@ -378,6 +398,230 @@ __global__ __launch_bounds__(256) void cross_sum_kernel(const double* pf, int Tn
   sum[idx] = s;
 }
 
+struct HelmCol {
+  const float2* spec[4];      // half spectra of (u, v) of side a, then of side b (one-sided: the first two)
+  const float2* tw;
+  float su, sv;               // per-component scale
+  int N, logN, S, L;          // the slices of rapsd_ws
+  double* part;               // [F][S][NP][N/2 + 1], NP = 3 or 8
+};
+
+constexpr int HELM_PT = RAPSD_PTS / 256;                        // points per thread and batch
+
+// What a point idx of a batch that starts at line u0 needs: the signed wavenumbers (kx = u along W, ky along H), whether the
+// Nyquist rule applies, gk = weight / (2 N^2) and g = gk / k2 (0 at k2 = 0: the mean has neither part).
+struct HelmGeom {
+  float kx, ky, gk, g;
+  bool nyq;
+};
+
+__device__ __forceinline__ HelmGeom helm_geom(int idx, int u0, int N, int logN) {
+  const int u = u0 + (idx >> logN), v = idx & (N - 1);
+  const int sv = v <= N / 2 ? v : v - N;
+  const int k2 = u * u + sv * sv;
+  HelmGeom h;
+  h.kx = (float)u;
+  h.ky = (float)sv;
+  h.nyq = u == N / 2 || v == N / 2;
+  h.gk = 0.5f / ((float)N * (float)N) * (u == 0 || u == N / 2 ? 1.f : 2.f);   // powers of two: exact
+  h.g = k2 > 0 ? h.gk / (float)k2 : 0.f;
+  return h;
+}
+
+// The rotational and divergent co-products of one point, R = kx V - ky U, D = kx U + ky V of each side:
+//   rot = Re(Ra conj Rb) g,  div = Re(Da conj Db) g;  on a Nyquist line (see the header) the sum without the cross term:
+//   rot = (kx^2 Re(Va conj Vb) + ky^2 Re(Ua conj Ub)) g,  div = (kx^2 Re(Ua conj Ub) + ky^2 Re(Va conj Vb)) g.
+// Called with b = a it gives a side's own rot and div, by the same operations: the co-planes of (a, a) equal a's planes.
+__device__ __forceinline__ void helm_products(const HelmGeom& h, float2 Ua, float2 Va, float2 Ub, float2 Vb, float& rot,
+                                              float& div) {
+  if (h.nyq) {
+    const float uu = fmaf(Ua.x, Ub.x, Ua.y * Ub.y), vv = fmaf(Va.x, Vb.x, Va.y * Vb.y);
+    const float kx2 = h.kx * h.kx, ky2 = h.ky * h.ky;
+    rot = fmaf(kx2, vv, ky2 * uu) * h.g;
+    div = fmaf(kx2, uu, ky2 * vv) * h.g;
+  } else {
+    const float2 Ra = make_float2(fmaf(h.kx, Va.x, -(h.ky * Ua.x)), fmaf(h.kx, Va.y, -(h.ky * Ua.y)));
+    const float2 Rb = make_float2(fmaf(h.kx, Vb.x, -(h.ky * Ub.x)), fmaf(h.kx, Vb.y, -(h.ky * Ub.y)));
+    const float2 Da = make_float2(fmaf(h.kx, Ua.x, h.ky * Va.x), fmaf(h.kx, Ua.y, h.ky * Va.y));
+    const float2 Db = make_float2(fmaf(h.kx, Ub.x, h.ky * Vb.x), fmaf(h.kx, Ub.y, h.ky * Vb.y));
+    rot = fmaf(Ra.x, Rb.x, Ra.y * Rb.y) * h.g;
+    div = fmaf(Da.x, Db.x, Da.y * Db.y) * h.g;
+  }
+}
+
+// One side of a batch: nl lines of U^ and of V^ through fft_lds (U^'s transformed lines parked in buf[2] as in
+// cross_col_kernel), then each thread's HELM_PT points (idx = threadIdx.x + 256 i, the same points in every batch and for
+// either side): the scaled U, V and their ke, rot, div in fp32.  ke and rot go straight into the FFT's free buffer, div waits
+// in registers until every thread has read its U and V and then goes over buf[2].  MODE 0: nothing else.  MODE 1 (side a of a
+// pair): the scaled U, V are handed out in Ua, Va.  MODE 2 (side b): the co-products with the Ua, Va handed in are formed next
+// to b's own and stored as planes 3 and 4.  Ends behind a barrier with pl[] = the planes (RAPSD_PTS floats each).
+template <int MODE>
+__device__ __forceinline__ void helm_side(float2 (*buf)[RAPSD_PTS], const float2* tw, const float2* lu, const float2* lv, int nl,
+                                          int u0, int N, int logN, float su, float sv, float2 (&Ua)[HELM_PT], float2 (&Va)[HELM_PT],
+                                          const float* (&pl)[5]) {
+  cross_load_lines(buf[0], lu, nl, logN);
+  __syncthreads();
+  int r = fft_lds(buf, tw, N, logN);
+  for (int idx = threadIdx.x; idx < RAPSD_PTS; idx += 256) buf[2][idx] = buf[r][idx];
+  __syncthreads();                                              // V^'s lines overwrite buf[0]
+  cross_load_lines(buf[0], lv, nl, logN);
+  __syncthreads();
+  r = fft_lds(buf, tw, N, logN);
+  float* free1 = reinterpret_cast<float*>(buf[r ^ 1]);          // the last stage's source: nobody reads it any more
+  float div[HELM_PT], co_rot[HELM_PT], co_div[HELM_PT];
+#pragma unroll
+  for (int i = 0; i < HELM_PT; ++i) {
+    const int idx = threadIdx.x + 256 * i;
+    const float2 x = buf[2][idx], y = buf[r][idx];
+    const float2 U = make_float2(x.x * su, x.y * su), V = make_float2(y.x * sv, y.y * sv);
+    const HelmGeom h = helm_geom(idx, u0, N, logN);
+    float rot;
+    helm_products(h, U, V, U, V, rot, div[i]);
+    free1[idx] = (fmaf(U.x, U.x, U.y * U.y) + fmaf(V.x, V.x, V.y * V.y)) * h.gk;
+    free1[RAPSD_PTS + idx] = rot;
+    if (MODE == 1) { Ua[i] = U; Va[i] = V; }
+    if (MODE == 2) helm_products(h, Ua[i], Va[i], U, V, co_rot[i], co_div[i]);
+  }
+  __syncthreads();                                              // every U and V is read: planes go over buf[2] and buf[r]
+  float* free2 = reinterpret_cast<float*>(buf[2]);
+  float* free3 = reinterpret_cast<float*>(buf[r]);
+#pragma unroll
+  for (int i = 0; i < HELM_PT; ++i) {
+    const int idx = threadIdx.x + 256 * i;
+    free2[idx] = div[i];
+    if (MODE == 2) {
+      free2[RAPSD_PTS + idx] = co_rot[i];
+      free3[idx] = co_div[i];
+    }
+  }
+  __syncthreads();
+  pl[0] = free1; pl[1] = free1 + RAPSD_PTS; pl[2] = free2; pl[3] = free2 + RAPSD_PTS; pl[4] = free3;
+}
+
+// Ring sums of planes pl[P0 .. P0 + NP) (LDS, RAPSD_PTS floats each) over the nl lines of a batch: rapsd_col_kernel's loop order
+// and fp64 accumulation, one independent sum per plane, so a plane's bits do not depend on which planes are summed next to it.
+template <int P0, int NP>
+__device__ __forceinline__ void helm_ring_sums(const float* const (&pl)[5], int u0, int nl, int N, int logN, int K,
+                                               double (*acc)[RAPSD_KQ]) {
+  for (int j = 0; j < nl; ++j) {
+    const int o = j << logN;
+#pragma unroll
+    for (int q = 0; q < RAPSD_KQ; ++q) {
+      const int k = threadIdx.x + 256 * q;
+      if (k >= K) continue;
+      int vmin, vmax;
+      ring_span(u0 + j, k, N, vmin, vmax);
+      double s[NP];
+#pragma unroll
+      for (int p = 0; p < NP; ++p) s[p] = 0.0;
+      for (int v = vmin; v <= vmax; ++v) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) s[p] += (double)pl[P0 + p][o + v];
+        if (v != 0 && v != N / 2) {
+#pragma unroll
+          for (int p = 0; p < NP; ++p) s[p] += (double)pl[P0 + p][o + N - v];
+        }
+      }
+#pragma unroll
+      for (int p = 0; p < NP; ++p) acc[p][q] += s[p];
+    }
+  }
+}
+
+template <int NP>
+__device__ __forceinline__ void helm_write_part(double* out, int K, const double (*acc)[RAPSD_KQ]) {
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int q = 0; q < RAPSD_KQ; ++q) {
+      const int k = threadIdx.x + 256 * q;
+      if (k < K) out[p * K + k] = acc[p][q];
+    }
+}
+
+// One-sided Helmholtz spectra.  LDS as cross_col_kernel: 3 x 16 KB line buffers + 16 KB twiddles = 64 KB, two workgroups per CU.
+__global__ __launch_bounds__(256, 2) void helm_col_kernel(HelmCol a) {
+  __shared__ float2 buf[3][RAPSD_PTS];
+  __shared__ float2 tw[DG_RAPSD_MAX_N];
+  const int N = a.N, logN = a.logN, nfft = RAPSD_PTS >> logN, K = N / 2 + 1;
+  const long long f = blockIdx.x / a.S;
+  const int s = blockIdx.x % a.S;
+  const int u_end = min(K, (s + 1) * a.L);
+  for (int m = threadIdx.x; m < N; m += 256) tw[m] = a.tw[m];
+  double acc[3][RAPSD_KQ];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int q = 0; q < RAPSD_KQ; ++q) acc[p][q] = 0.0;
+  for (int u0 = s * a.L; u0 < u_end; u0 += nfft) {
+    const int nl = min(nfft, u_end - u0);
+    const long long line0 = (f * K + u0) * N;
+    float2 U[HELM_PT], V[HELM_PT];                              // unused in MODE 0
+    const float* pl[5];
+    helm_side<0>(buf, tw, a.spec[0] + line0, a.spec[1] + line0, nl, u0, N, logN, a.su, a.sv, U, V, pl);
+    helm_ring_sums<0, 3>(pl, u0, nl, N, logN, K, acc);
+    __syncthreads();                                            // the next batch overwrites buf
+  }
+  helm_write_part<3>(a.part + (f * a.S + s) * 3 * K, K, acc);
+}
+
+// Paired Helmholtz spectra, planes [ke_a, rot_a, div_a, ke_b, rot_b, div_b, co_rot, co_div].  Side a runs first and is ring-summed
+// exactly as in helm_col_kernel; its scaled U, V stay in registers (4 floats x HELM_PT points = 32 VGPRs: R and D follow from
+// them, and the Nyquist rule needs the components themselves) while side b runs through the same three LDS buffers.  Side b's
+// three planes and the two co-planes are then ring-summed in one walk over the lines.  LDS stays at 64 KB; the accumulators are
+// 8 x RAPSD_KQ doubles per thread, all eight planes in one pass: 248 VGPRs, no spill at two workgroups per CU.
+__global__ __launch_bounds__(256, 2) void helm_cross_col_kernel(HelmCol a) {
+  __shared__ float2 buf[3][RAPSD_PTS];
+  __shared__ float2 tw[DG_RAPSD_MAX_N];
+  const int N = a.N, logN = a.logN, nfft = RAPSD_PTS >> logN, K = N / 2 + 1;
+  const long long f = blockIdx.x / a.S;
+  const int s = blockIdx.x % a.S;
+  const int u_end = min(K, (s + 1) * a.L);
+  for (int m = threadIdx.x; m < N; m += 256) tw[m] = a.tw[m];
+  double acc[8][RAPSD_KQ];
+#pragma unroll
+  for (int p = 0; p < 8; ++p)
+#pragma unroll
+    for (int q = 0; q < RAPSD_KQ; ++q) acc[p][q] = 0.0;
+  for (int u0 = s * a.L; u0 < u_end; u0 += nfft) {
+    const int nl = min(nfft, u_end - u0);
+    const long long line0 = (f * K + u0) * N;
+    float2 Ua[HELM_PT], Va[HELM_PT];
+    const float* pl[5];
+    helm_side<1>(buf, tw, a.spec[0] + line0, a.spec[1] + line0, nl, u0, N, logN, a.su, a.sv, Ua, Va, pl);
+    helm_ring_sums<0, 3>(pl, u0, nl, N, logN, K, acc);
+    __syncthreads();                                            // side b's lines overwrite buf
+    helm_side<2>(buf, tw, a.spec[2] + line0, a.spec[3] + line0, nl, u0, N, logN, a.su, a.sv, Ua, Va, pl);
+    helm_ring_sums<0, 5>(pl, u0, nl, N, logN, K, acc + 3);
+    __syncthreads();                                            // the next batch overwrites buf
+  }
+  helm_write_part<8>(a.part + (f * a.S + s) * 8 * K, K, acc);
+}
+
+// one thread per (field, plane, ring): the slices in order (cross_field_kernel for NP planes)
+__global__ __launch_bounds__(256) void helm_field_kernel(const double* part, const double* cnt, long long F, int S, int NP, int K,
+                                                         double* pf, double* per_field) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= F * NP * K) return;
+  const long long f = idx / (NP * K);
+  const int pk = (int)(idx % (NP * K));                         // plane * K + ring
+  const double* q = part + f * S * NP * K + pk;
+  double s = 0.0;
+  for (int i = 0; i < S; ++i) s += q[(long long)i * NP * K];
+  s /= cnt[pk % K];
+  pf[idx] = s;
+  if (per_field) per_field[idx] = s;
+}
+
+// one thread per (plane, ring): the fields in t order
+__global__ __launch_bounds__(256) void helm_sum_kernel(const double* pf, int Tn, int NPK, double* sum) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= NPK) return;
+  double s = 0.0;
+  for (int t = 0; t < Tn; ++t) s += pf[(long long)t * NPK + idx];
+  sum[idx] = s;
+}
+
 // workspace: twiddles, counts, spec, slice partials, per-field spectra (each 256-byte aligned)
 struct RapsdWs {
   size_t tw, cnt, spec, part, pf, bytes;
@@ -441,7 +685,109 @@ void launch_row(const dg_eof_fields* x, int N, long long npairs, long long row_b
   else hipLaunchKernelGGL(rapsd_row_kernel<bf16_t>, dim3((unsigned)row_blocks), dim3(256), 0, st, r);
 }
 
+// Helmholtz spectra: twiddles, counts, the half spectra of (u, v) of each side, slice partials [T][S][NP][K], per-field
+// [T][NP][K]; one field per pair, so S and L are rapsd_ws(T, N)'s
+struct HelmWs {
+  size_t tw, cnt, spec[4], part, pf, bytes;
+  int S, L;
+};
+
+HelmWs helm_ws(long long T, int N, int sides) {
+  const RapsdWs r = rapsd_ws(T, N);
+  const int K = N / 2 + 1, NP = sides == 2 ? 8 : 3;
+  HelmWs w;
+  w.S = r.S;
+  w.L = r.L;
+  w.tw = 0;
+  w.cnt = w.tw + align256((size_t)N * 8);
+  size_t at = w.cnt + align256((size_t)K * 8);
+  for (int i = 0; i < 4; ++i) {
+    w.spec[i] = at;
+    if (i < 2 * sides) at += align256((size_t)T * K * N * 8);
+  }
+  w.part = at;
+  w.pf = w.part + align256((size_t)T * w.S * NP * K * 8);
+  w.bytes = w.pf + align256((size_t)T * NP * K * 8);
+  return w;
+}
+
+bool helm_side_ok(const dg_eof_fields* x, int cu, int cv, int N) {
+  return rapsd_fields_ok(x, N) && cu >= 0 && cv >= 0 && cu != cv && cu < x->C && cv < x->C;
+}
+
+// the one-channel descriptor of channel c of x
+dg_eof_fields helm_channel(const dg_eof_fields* x, int c) {
+  dg_eof_fields y = *x;
+  y.base = reinterpret_cast<const char*>(x->base) + (long long)c * x->ld_c * (x->dtype == DG_F32 ? 4 : 2);
+  y.C = 1;
+  return y;
+}
+
+int helm_run(const dg_eof_fields* a, const dg_eof_fields* b, int cu, int cv, const float* scale, int N, void* ws,
+             double* per_field, double* sum, void* stream) {
+  const int sides = b ? 2 : 1, NP = b ? 8 : 3;
+  const long long T = a->T;
+  const int K = N / 2 + 1, logN = __builtin_ctz(N), nfft = RAPSD_PTS / N;
+  const HelmWs w = helm_ws(T, N, sides);
+  const long long npairs = T * (N / 2);
+  const long long row_blocks = (npairs + nfft - 1) / nfft, col_blocks = T * w.S;
+  if (row_blocks > 0x7fffffffLL || col_blocks > 0x7fffffffLL || T * NP * K > 0x7fffffffLL * 256LL) return DG_ERR_BAD_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  char* base = reinterpret_cast<char*>(ws);
+  float2* tw = reinterpret_cast<float2*>(base + w.tw);
+  double* cnt = reinterpret_cast<double*>(base + w.cnt);
+  double* part = reinterpret_cast<double*>(base + w.part);
+  double* pf = reinterpret_cast<double*>(base + w.pf);
+  hipLaunchKernelGGL(rapsd_twiddle_kernel, dim3((N + 255) / 256), dim3(256), 0, st, tw, N);
+  hipLaunchKernelGGL(rapsd_count_kernel, dim3((K + 255) / 256), dim3(256), 0, st, cnt, N);
+  HelmCol c;
+  for (int i = 0; i < 4; ++i) c.spec[i] = reinterpret_cast<float2*>(base + w.spec[i]);
+  for (int i = 0; i < 2 * sides; ++i) {
+    const dg_eof_fields x = helm_channel(i < 2 ? a : b, i % 2 ? cv : cu);
+    launch_row(&x, N, npairs, row_blocks, tw, reinterpret_cast<float2*>(base + w.spec[i]), st);
+  }
+  c.tw = tw; c.su = scale[0]; c.sv = scale[1]; c.N = N; c.logN = logN; c.S = w.S; c.L = w.L; c.part = part;
+  if (b) hipLaunchKernelGGL(helm_cross_col_kernel, dim3((unsigned)col_blocks), dim3(256), 0, st, c);
+  else hipLaunchKernelGGL(helm_col_kernel, dim3((unsigned)col_blocks), dim3(256), 0, st, c);
+  hipLaunchKernelGGL(helm_field_kernel, dim3((unsigned)((T * NP * K + 255) / 256)), dim3(256), 0, st, (const double*)part,
+                     (const double*)cnt, T, w.S, NP, K, pf, per_field);
+  if (sum)
+    hipLaunchKernelGGL(helm_sum_kernel, dim3((unsigned)((NP * K + 255) / 256)), dim3(256), 0, st, (const double*)pf, (int)T, NP * K,
+                       sum);
+  return dg_check_launch();
+}
+
+bool helm_scale_ok(const float* scale) {
+  return scale && std::isfinite(scale[0]) && std::isfinite(scale[1]) && scale[0] != 0.f && scale[1] != 0.f;
+}
+
 }  // namespace
+
+extern "C" size_t dg_helmholtz_ws_bytes(int T, int N) {
+  if (T < 1 || !rapsd_n_ok(N)) return 0;
+  return helm_ws(T, N, 1).bytes;
+}
+
+extern "C" int dg_helmholtz(const dg_eof_fields* x, int cu, int cv, const float scale[2], int N, void* ws, double* per_field,
+                            double* sum, void* stream) {
+  if (!ws || !rapsd_n_ok(N) || !helm_side_ok(x, cu, cv, N) || !helm_scale_ok(scale)) return DG_ERR_BAD_SHAPE;
+  if (x->dtype != DG_F32 && x->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
+  return helm_run(x, nullptr, cu, cv, scale, N, ws, per_field, sum, stream);
+}
+
+extern "C" size_t dg_helmholtz_cross_ws_bytes(int T, int N) {
+  if (T < 1 || !rapsd_n_ok(N)) return 0;
+  return helm_ws(T, N, 2).bytes;
+}
+
+extern "C" int dg_helmholtz_cross(const dg_eof_fields* a, const dg_eof_fields* b, int cu, int cv, const float scale[2], int N,
+                                  void* ws, double* per_field, double* sum, void* stream) {
+  if (!ws || !rapsd_n_ok(N) || !helm_side_ok(a, cu, cv, N) || !helm_side_ok(b, cu, cv, N) || a->T != b->T || a->C != b->C ||
+      !helm_scale_ok(scale))
+    return DG_ERR_BAD_SHAPE;
+  if ((a->dtype != DG_F32 && a->dtype != DG_BF16) || (b->dtype != DG_F32 && b->dtype != DG_BF16)) return DG_ERR_BAD_DTYPE;
+  return helm_run(a, b, cu, cv, scale, N, ws, per_field, sum, stream);
+}
 
 extern "C" size_t dg_rapsd_ws_bytes(int T, int C, int N) {
   if (T < 1 || C < 1 || C > DG_EOF_MAX_C || !rapsd_n_ok(N)) return 0;

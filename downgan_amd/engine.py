@@ -1237,7 +1237,7 @@ class TrainEngine:
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
     def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                     coherence=None, increments=None, hist_maps=None, temporal=None):
+                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1263,7 +1263,9 @@ class TrainEngine:
         ``hist_maps``: a paired ``gridhist.GridHist`` that likewise receives (fine[:n], fake[:n]) in one call: the per-gridpoint
         histograms of both series (local quantiles, W1 / KS per pixel).
         ``temporal``: a paired ``temporal.Temporal`` that likewise receives (fine[:n], fake[:n]) in one call, as the next n times
-        of its series: the caller feeds the batches in time order."""
+        of its series: the caller feeds the batches in time order.
+        ``helmholtz``: a ``spectra.HelmholtzSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the rotational and
+        divergent kinetic energy spectra of both wind fields and the coherence of each part."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1277,6 +1279,8 @@ class TrainEngine:
             spectra[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if coherence is not None:
             coherence.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if helmholtz is not None:
+            helmholtz.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if distributions is not None:
             distributions[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
             distributions[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)

@@ -882,6 +882,44 @@ class HipOps:
         check(self.lib.dg_cross_rapsd(C.byref(fa), C.byref(fb), int(N), _ptr(ws), _ptr(per_field), _ptr(sum), self._stream()),
               "dg_cross_rapsd")
 
+    def helmholtz_ws_bytes(self, T, N):
+        """Workspace bytes of one dg_helmholtz call over T fields, N x N (0: not a valid shape)."""
+        return int(self.lib.dg_helmholtz_ws_bytes(int(T), int(N)))
+
+    def helmholtz_cross_ws_bytes(self, T, N):
+        """Workspace bytes of one dg_helmholtz_cross call over T pairs, N x N (0: not a valid shape)."""
+        return int(self.lib.dg_helmholtz_cross_ws_bytes(int(T), int(N)))
+
+    def _helmholtz(self, fa, fb, cu, cv, scale, N, per_field, sum):
+        K, NP = N // 2 + 1, 3 if fb is None else 8
+        for out, n in ((per_field, fa.T * NP * K), (sum, NP * K)):
+            assert out is None or (out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n and out.is_cuda)
+        nb = self.helmholtz_ws_bytes(fa.T, N) if fb is None else self.helmholtz_cross_ws_bytes(fa.T, N)
+        assert nb > 0, (fa.T, N)
+        ws = getattr(self, "_rapsd_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._rapsd_ws = ws = None
+            self._rapsd_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        sc = (C.c_float * 2)(float(scale[0]), float(scale[1]))
+        if fb is None:
+            check(self.lib.dg_helmholtz(C.byref(fa), int(cu), int(cv), sc, int(N), _ptr(ws), _ptr(per_field), _ptr(sum),
+                                        self._stream()), "dg_helmholtz")
+        else:
+            assert (fa.T, fa.C, fa.P) == (fb.T, fb.C, fb.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+            check(self.lib.dg_helmholtz_cross(C.byref(fa), C.byref(fb), int(cu), int(cv), sc, int(N), _ptr(ws), _ptr(per_field),
+                                              _ptr(sum), self._stream()), "dg_helmholtz_cross")
+
+    def helmholtz(self, f, cu, cv, scale, N, per_field=None, sum=None):
+        """Ring-averaged Helmholtz spectra of the vector field (channel cu, channel cv) of the N x N fields of the descriptor
+        ``f``, each component times scale[0], scale[1]: per_field [T, 3, N/2+1] and / or sum [3, N/2+1] (over the T fields, in
+        order), planes ke, rot, div; fp64 contiguous, either may be None.  The workspace is ``rapsd``'s cached buffer."""
+        self._helmholtz(f, None, cu, cv, scale, N, per_field, sum)
+
+    def helmholtz_cross(self, fa, fb, cu, cv, scale, N, per_field=None, sum=None):
+        """The paired call: per_field [T, 8, N/2+1] and / or sum [8, N/2+1], planes ke, rot, div of ``fa``, of ``fb``, then
+        co_rot, co_div (the same T, C and N, layouts and dtypes independent).  The workspace is ``rapsd``'s cached buffer."""
+        self._helmholtz(fa, fb, cu, cv, scale, N, per_field, sum)
+
     # ------------------------------------------------------------------ value histograms (csrc/histogram.hip)
     def hist_ws_bytes(self, f, spec):
         """Workspace bytes of one dg_hist call over the descriptor ``f`` with the _lib.HistSpec ``spec`` (0: invalid)."""

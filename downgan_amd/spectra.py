@@ -20,6 +20,13 @@ The RAPSD is phase-blind: a generator can match it perfectly while every small-s
 from which follow the ``coherence`` s2 / sqrt(s0 s1), the ``error_spectrum`` s0 + s1 - 2 s2 (the ring power of a - b) and the
 ``effective_resolution``: the last wavenumber down to which the coherence stays above a threshold, i.e. the scale below which
 the generated field is only plausible texture.  ``CrossSpectrum`` is the accumulator (``WassersteinGAN.log_coherence``).
+
+All of the above look at one channel at a time.  ``helmholtz_rapsd`` takes the wind as a vector: the kinetic energy per wavenumber
+and its split into a rotational (vortical) and a divergent part, which depends on the phase relation between the two components'
+spectra; ``helmholtz_cross`` adds, for the paired real and generated winds, the co-spectra of each part, from which follow
+``helmholtz_coherence`` and an ``effective_resolution`` per part -- down to which scale the generator reproduces the real vortical
+flow, and down to which the divergent one -- next to ``divergent_fraction`` and ``spectral_slope``.  ``HelmholtzSpectrum`` is the
+accumulator (``WassersteinGAN.log_helmholtz``).
 """
 from __future__ import annotations
 
@@ -368,6 +375,239 @@ class RadialSpectrum:
         """float64 [C, K]: the mean spectrum of every field added (and, after ``reduce_``, of every rank)."""
         if self.count == 0:
             raise ValueError("RadialSpectrum.mean: no field was added")
+        return self.sums / self._acc[-1]
+
+    def reduce_(self, dist):
+        """Sum the sums and counts over the data-parallel ranks of ``dist`` (downgan_amd.dist.Dist), once, in place."""
+        if dist is not None and dist.world_size > 1:
+            dist.allreduce_sum_(self._acc)
+        return self
+
+
+# ---------------------------------------------------------------------------------------------------- Helmholtz spectra
+HELM_PLANES = ("ke", "rot", "div")
+HELM_CROSS_PLANES = ("ke_real", "rot_real", "div_real", "ke_fake", "rot_fake", "div_fake", "co_rot", "co_div")
+
+
+def _helm_pair(pair, Cn=None):
+    """ValueError unless ``pair`` is two distinct channel indices (below Cn when given) -> (cu, cv)."""
+    try:
+        cu, cv = pair
+        ok = all(isinstance(c, (int, np.integer)) and not isinstance(c, bool) for c in (cu, cv))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"Helmholtz spectra take pair = (channel of u, channel of v), two integers (got {pair!r})")
+    top = C_MAX if Cn is None else Cn
+    if cu == cv or not (0 <= cu < top and 0 <= cv < top):
+        raise ValueError(f"Helmholtz spectra need a pair of two different channels in [0, {top}) (got pair = {tuple(pair)})")
+    return int(cu), int(cv)
+
+
+def _helm_scale(scale, rows_up):
+    """ValueError unless ``scale`` is None or two finite non-zero numbers -> (su, sv), sv negated for rows that run downward."""
+    if scale is None:
+        su, sv = 1.0, 1.0
+    else:
+        try:
+            su, sv = (float(v) for v in scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"Helmholtz spectra take scale = (scale of u, scale of v) (got {scale!r})") from None
+        if not (np.isfinite(su) and np.isfinite(sv) and su != 0.0 and sv != 0.0):
+            raise ValueError(f"Helmholtz spectra need finite non-zero scales (got scale = {(su, sv)})")
+    return su, sv if rows_up else -sv
+
+
+def _helm_fields(x, channels, nhwc, pair):
+    x, nhwc, Cn, T, N = _fields(x, channels, nhwc)
+    if Cn < 2:
+        raise ValueError(f"Helmholtz spectra need a vector field: C >= 2 channels (got C = {Cn})")
+    return x, nhwc, Cn, T, N, _helm_pair(pair, Cn)
+
+
+def _helm_chunk(o, T, N, paired):
+    """Fields (pairs) per library call: the fewest calls whose workspace stays within WS_CAP bytes, the T spread evenly over
+    them (as ``_cross_chunk``)."""
+    nbytes = o.helmholtz_cross_ws_bytes if paired else o.helmholtz_ws_bytes
+    tc = min(T, max(1, WS_CAP // max(1, nbytes(1, N))))
+    while tc > 1 and nbytes(tc, N) > WS_CAP:
+        tc -= 1
+    calls = -(-T // tc)
+    return -(-T // calls)
+
+
+def _helm_run(o, a, b, Cn, T, N, cu, cv, sc, total=None, per_field=None):
+    """One-sided (b None) or paired call over the T fields in chunks: ``total`` [NP, K] += the chunk sums in order, or
+    ``per_field`` [T, NP, K] filled."""
+    tc = _helm_chunk(o, T, N, b is not None)
+    part = None if total is None else torch.empty_like(total)
+    for t0 in range(0, T, tc):
+        kw = {"sum": part} if per_field is None else {"per_field": per_field[t0:t0 + tc]}
+        xa, fa = _descriptor(o, a[0][t0:t0 + tc], a[1], Cn)
+        if b is None:
+            o.helmholtz(fa, cu, cv, sc, N, **kw)
+        else:
+            xb, fb = _descriptor(o, b[0][t0:t0 + tc], b[1], Cn)
+            o.helmholtz_cross(fa, fb, cu, cv, sc, N, **kw)
+        if total is not None:
+            total += part
+
+
+def helmholtz_rapsd(x, pair=(0, 1), scale=None, rows_up=True, channels=None, nhwc=False, per_field=False, ops=None):
+    """Helmholtz decomposition of the kinetic energy spectrum of a series of square vector fields on the GPU.
+
+    x: as ``rapsd``'s, with C >= 2 channels; ``pair`` = (channel of u, channel of v).  u points along increasing column index
+    (the last axis) and v along increasing row index; ``rows_up=False`` says that the rows run the other way (v points toward
+    decreasing row index, e.g. a northward v on rows stored north to south) and negates v's scale.  A field whose first wind
+    component points along the rows is the same call with the pair exchanged.  With U = su fft2(u), V = sv fft2(v), the signed
+    integer wavenumbers kx (along W), ky (along H) and k2 = kx^2 + ky^2:
+
+        ke = (|U|^2 + |V|^2) / (2 N^2),  div = |kx U + ky V|^2 / (2 k2 N^2),  rot = |kx V - ky U|^2 / (2 k2 N^2)
+
+    (rot = div = 0 at k2 = 0), averaged over ``rapsd``'s rings: rot + div = ke on every ring k >= 1.
+    ``scale`` = (su, sv), None = (1, 1).  UNLIKE every scalar spectrum here the decomposition is NOT invariant under per-channel
+    scaling: on z-scored channels the split is only meaningful with ``scale = (std_u, std_v)``, the standard deviations the
+    channels were divided by, so that both components are in the same physical unit again.
+    Returns float64 [3, N/2 + 1] (planes ke, rot, div), the mean over T, or [T, 3, N/2 + 1] with ``per_field``."""
+    sc = _helm_scale(scale, rows_up)
+    x, nhwc, Cn, T, N, (cu, cv) = _helm_fields(x, channels, nhwc, pair)
+    o = ops if ops is not None else _default_ops(x.device)
+    K = N // 2 + 1
+    if per_field:
+        out = torch.empty(T, 3, K, dtype=torch.float64, device=x.device)
+        _helm_run(o, (x, nhwc), None, Cn, T, N, cu, cv, sc, per_field=out)
+        return out
+    total = torch.zeros(3, K, dtype=torch.float64, device=x.device)
+    _helm_run(o, (x, nhwc), None, Cn, T, N, cu, cv, sc, total=total)
+    return total / T
+
+
+def _helm_sides(a, b, pair, nhwc, nhwc_b, channels=None):
+    sa, sb, Cn, T, N = _pair(a, b, channels, nhwc, nhwc_b)
+    if Cn < 2:
+        raise ValueError(f"Helmholtz spectra need a vector field: C >= 2 channels (got C = {Cn})")
+    return sa, sb, Cn, T, N, _helm_pair(pair, Cn)
+
+
+def helmholtz_cross(a, b, pair=(0, 1), scale=None, rows_up=True, nhwc=False, nhwc_b=None, per_field=False, ops=None,
+                    channels=None):
+    """Helmholtz spectra of the PAIRED vector fields a (real) and b (generated) and the co-spectra of their rotational and of
+    their divergent parts (``pair``, ``scale``, ``rows_up`` as ``helmholtz_rapsd``, layouts and ``channels`` as ``cross_rapsd``:
+    of a padded NHWC store only the leading ``channels`` count, and the pair lies among them).
+
+    Returns float64 [8, N/2 + 1], the mean over T of the planes ke_a, rot_a, div_a, ke_b, rot_b, div_b, co_rot, co_div, or
+    [T, 8, N/2 + 1] with ``per_field``; co_rot = Re(Ra conj Rb) / (2 k2 N^2) with R = kx V - ky U of each side, co_div likewise
+    with D = kx U + ky V, so |co_x| <= sqrt(x_a x_b) on every ring and co_rot + co_div = (co_u + co_v) / 2 of ``cross_rapsd`` on
+    the scaled channels.  Per library call planes 0-5 equal ``helmholtz_rapsd`` of a and of b bit for bit."""
+    sc = _helm_scale(scale, rows_up)
+    sa, sb, Cn, T, N, (cu, cv) = _helm_sides(a, b, pair, nhwc, nhwc_b, channels)
+    dev = sa[0].device
+    o = ops if ops is not None else _default_ops(dev)
+    K = N // 2 + 1
+    if per_field:
+        out = torch.empty(T, 8, K, dtype=torch.float64, device=dev)
+        _helm_run(o, sa, sb, Cn, T, N, cu, cv, sc, per_field=out)
+        return out
+    total = torch.zeros(8, K, dtype=torch.float64, device=dev)
+    _helm_run(o, sa, sb, Cn, T, N, cu, cv, sc, total=total)
+    return total / T
+
+
+def _helm_planes(s):
+    s = _host(s)
+    if s.ndim < 2 or s.shape[-2] not in (3, 8):
+        raise ValueError(f"Helmholtz spectra are [..., 3, K] or [..., 8, K] (got shape {s.shape})")
+    return s
+
+
+def divergent_fraction(s):
+    """div / (rot + div) per wavenumber, NaN on ring 0 (and wherever both vanish): Helmholtz spectra [..., 3, K] -> numpy
+    float64 [..., K]; paired spectra [..., 8, K] -> [..., 2, K], side a then side b."""
+    s = _helm_planes(s)
+    if s.shape[-2] == 8:
+        return np.stack([divergent_fraction(s[..., 0:3, :]), divergent_fraction(s[..., 3:6, :])], axis=-2)
+    rot, div = s[..., 1, :], s[..., 2, :]
+    den = rot + div
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = np.where(den == 0, np.nan, div / den)
+    out[..., 0] = np.nan
+    return out
+
+
+def helmholtz_coherence(s):
+    """co_rot / sqrt(rot_a rot_b) and co_div / sqrt(div_a div_b) per wavenumber: paired Helmholtz spectra [..., 8, K] -> numpy
+    float64 [..., 2, K] (rot, div); NaN where a denominator is 0 (ring 0).  ``effective_resolution`` takes each row."""
+    s = _helm_planes(s)
+    if s.shape[-2] != 8:
+        raise ValueError(f"helmholtz_coherence takes paired spectra [..., 8, K] (got shape {s.shape})")
+    rows = []
+    for pa, pb, pc in ((1, 4, 6), (2, 5, 7)):
+        den = np.sqrt(s[..., pa, :] * s[..., pb, :])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rows.append(np.where(den == 0, np.nan, s[..., pc, :] / den))
+    return np.stack(rows, axis=-2)
+
+
+def spectral_slope(p, kmin, kmax):
+    """Least-squares slope of log p against log k over the rings kmin <= k <= kmax (1 <= kmin < kmax <= K - 1): spectra
+    [..., K] -> numpy float64 [...] ([K] -> a float); -3 for p ~ k^-3.  NaN where a ring of the band is not positive."""
+    p = _host(p)
+    if p.ndim < 1 or not (isinstance(kmin, (int, np.integer)) and isinstance(kmax, (int, np.integer))
+                          and 1 <= kmin < kmax <= p.shape[-1] - 1):
+        raise ValueError(f"spectral_slope: a band 1 <= kmin < kmax <= K - 1 of spectra [..., K] (got kmin = {kmin}, kmax = {kmax}, "
+                         f"shape {p.shape})")
+    x = np.log(np.arange(kmin, kmax + 1, dtype=np.float64))
+    x = x - x.mean()
+    with np.errstate(divide="ignore", invalid="ignore"):
+        y = np.log(np.where(p[..., kmin:kmax + 1] > 0, p[..., kmin:kmax + 1], np.nan))
+    out = (y * x).sum(axis=-1) / (x * x).sum()
+    return float(out) if out.ndim == 0 else out
+
+
+class HelmholtzSpectrum:
+    """Running mean of the paired Helmholtz spectra of N x N vector fields (``helmholtz_cross``): fp64 sums [8, K] and the pair
+    count stay on the device (one buffer, so ``reduce_`` is one all-reduce under data parallelism)."""
+
+    def __init__(self, N, pair=(0, 1), scale=None, rows_up=True, device="cuda:0", ops=None):
+        check_n(N)
+        self.pair = _helm_pair(pair)
+        self.scale = _helm_scale(scale, rows_up)
+        self.N, self.K = int(N), N // 2 + 1
+        self.device = torch.device(device)
+        self._ops = ops
+        self._acc = torch.zeros(8 * self.K + 1, dtype=torch.float64, device=self.device)
+
+    @property
+    def ops(self):
+        if self._ops is None:
+            self._ops = _default_ops(self.device)
+        return self._ops
+
+    @property
+    def sums(self):
+        return self._acc[:-1].view(8, self.K)
+
+    @property
+    def count(self):
+        """Number of pairs added so far."""
+        return int(round(float(self._acc[-1].item())))
+
+    def add(self, a, b, n_valid=None, nhwc=False, nhwc_b=None, channels=None):
+        """Add the spectra of the first ``n_valid`` (default: all) pairs of a batch (layouts as ``cross_rapsd``)."""
+        sa, sb, Cn, T, N, (cu, cv) = _helm_sides(a, b, self.pair, nhwc, nhwc_b, channels)
+        if N != self.N:
+            raise ValueError(f"HelmholtzSpectrum({self.N}) given fields of {N} x {N}")
+        n = T if n_valid is None else int(n_valid)
+        if not 1 <= n <= T:
+            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        _helm_run(self.ops, (sa[0][:n], sa[1]), (sb[0][:n], sb[1]), Cn, n, N, cu, cv, self.scale, total=self.sums)
+        self._acc[-1] += n
+        return self
+
+    def mean(self):
+        """float64 [8, K]: the mean spectra of every pair added (and, after ``reduce_``, of every rank)."""
+        if self.count == 0:
+            raise ValueError("HelmholtzSpectrum.mean: no field was added")
         return self.sums / self._acc[-1]
 
     def reduce_(self, dist):

@@ -541,6 +541,41 @@ int dg_rapsd_ring_counts(int N, int64_t* counts);
 size_t dg_cross_rapsd_ws_bytes(int T, int C, int N);
 int dg_cross_rapsd(const dg_eof_fields* a, const dg_eof_fields* b, int N, void* ws, double* per_field, double* sum, void* stream);
 
+/* ---- Helmholtz spectra (csrc/spectra.hip) -------------------------------------------------------------------------------
+ * What kind of motion carries the variance at a given scale?  The kinetic energy spectrum of a vector field (u, v) = channels
+ * (cu, cv) of the descriptor, split into its rotational and divergent parts.  N x N fields as above; scale[0], scale[1]: a factor
+ * per component (finite, non-zero, the sign allowed), U = scale[0] FFT2(u), V = scale[1] FFT2(v); kx = the signed integer
+ * frequency along W (the last axis), ky along H, k2 = kx^2 + ky^2:
+ *   ke  = (|U|^2 + |V|^2)  / (2 N^2)
+ *   div = |kx U + ky V|^2  / (2 k2 N^2)    (0 where k2 = 0)
+ *   rot = |kx V - ky U|^2  / (2 k2 N^2)    (0 where k2 = 0)
+ * averaged over the rings of dg_rapsd; rot + div = ke on every ring k >= 1.  The first component points along increasing column
+ * index, the second along increasing row index; a field whose first channel points along H is the same call with cu, cv
+ * exchanged, rows that run the other way are the same call with scale[1] negated.  The split is NOT invariant under
+ * per-channel scaling: on standardised channels pass their standard deviations.
+ * For a pair (a, b), with R = kx V - ky U and D = kx U + ky V of each side, also
+ *   co_rot = Re(Ra conj Rb) / (2 k2 N^2),  co_div = Re(Da conj Db) / (2 k2 N^2),   |co_x| <= sqrt(x_a x_b) per ring.
+ * Nyquist rule: a point of the half spectrum with u = N/2 or v = N/2 stands for two frequencies whose cross terms
+ * 2 kx ky Re(U conj V) cancel in the ring sum, so it contributes div ~ kx^2 |U|^2 + ky^2 |V|^2, rot ~ kx^2 |V|^2 + ky^2 |U|^2
+ * (the co-planes: the corresponding real parts); for real fields this equals the full-spectrum definition above.
+ * Row pass: dg_rapsd's, once per component and side; column pass: both components' lines of a slice in LDS, the planes formed
+ * per point in fp32, ring sums in fp64 in dg_rapsd's order.  No float atomics: two calls on the same data are bit-identical;
+ * planes 0-5 of dg_helmholtz_cross equal dg_helmholtz of a and of b bit for bit, and (a, a) gives co_rot = rot, co_div = div.
+ *
+ * dg_helmholtz_ws_bytes / dg_helmholtz_cross_ws_bytes: workspace bytes for T fields (pairs) (0 for an invalid shape); ~16 (32)
+ *   (N/2 + 1) N bytes per field (pair): the half spectra of both components (of both sides) plus small fp64 partials.
+ * dg_helmholtz: per_field[t][plane][k] (fp64 [T][3][K], planes ke, rot, div; may be NULL) and sum[plane][k] over t in t order
+ *   (fp64 [3][K], may be NULL).  cu != cv, both < x->C; x->P = N*N.
+ * dg_helmholtz_cross: per_field fp64 [T][8][K], sum fp64 [8][K], planes ke_a, rot_a, div_a, ke_b, rot_b, div_b, co_rot, co_div.
+ *   a and b agree in T, C and P; layouts and dtypes (fp32 / bf16) are independent.
+ * Bad shapes, channel indices or scales: DG_ERR_BAD_SHAPE; other dtypes: DG_ERR_BAD_DTYPE; both before any launch. */
+size_t dg_helmholtz_ws_bytes(int T, int N);
+int dg_helmholtz(const dg_eof_fields* x, int cu, int cv, const float scale[2], int N, void* ws, double* per_field, double* sum,
+                 void* stream);
+size_t dg_helmholtz_cross_ws_bytes(int T, int N);
+int dg_helmholtz_cross(const dg_eof_fields* a, const dg_eof_fields* b, int cu, int cv, const float scale[2], int N, void* ws,
+                       double* per_field, double* sum, void* stream);
+
 /* ---- Value histograms (csrc/histogram.hip) ------------------------------------------------------------------------------
  * The distribution check of a downscaling generator: per-channel histograms of real and generated fields, read in place
  * through the EOF descriptor (any T, P; NCHW fp32 / bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC
