@@ -148,7 +148,7 @@ class WassersteinGAN:
         return float(e._sc("gp_ret").item())
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                                  coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None):
+                                  coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
@@ -158,12 +158,15 @@ class WassersteinGAN:
         ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair; ``increments``: one ``increments.Increments`` fed the
         same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given); ``temporal``: one
         paired ``temporal.Temporal`` fed the same pair as the next times of its series (likewise only when given); ``helmholtz``:
-        one ``spectra.HelmholtzSpectrum`` fed the same pair (likewise only when given)."""
+        one ``spectra.HelmholtzSpectrum`` fed the same pair (likewise only when given); ``objects``: one paired
+        ``objects.Objects`` fed the same pair (likewise only when given)."""
         more = {} if hist_maps is None else {"hist_maps": hist_maps}
         if temporal is not None:
             more["temporal"] = temporal
         if helmholtz is not None:
             more["helmholtz"] = helmholtz
+        if objects is not None:
+            more["objects"] = objects
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -254,6 +257,12 @@ class WassersteinGAN:
     helmholtz_scale = None
     helmholtz_rows_up = True
     helmholtz_threshold = 0.5
+    # opt-in: object-based verification of the same (real, generated) pairs -- the connected exceedance objects per threshold
+    # (counts, area and mass distributions, per-object POD / FAR / CSI, the SAL score), reported per epoch in summary["objects"];
+    # objects_spec None = objects.ObjectSpec.zscore(n_predictands).  Every metrics pass then waits once for its object count
+    log_objects = False
+    objects_spec = None
+    objects_results = None       # the last epoch's {"train" / "test": objects.ObjectsResult} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -309,6 +318,12 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return Temporal(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
 
+    def _objects_acc(self, fine):
+        from ..objects import Objects, ObjectSpec
+        spec = self.objects_spec if self.objects_spec is not None else ObjectSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return Objects(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
     def _coherence_acc(self, fine):
         from ..spectra import CrossSpectrum
         dev = self._engine.ops.device if self._engine is not None else self.G.device
@@ -322,7 +337,7 @@ class WassersteinGAN:
 
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}, "helmholtz": {part: HelmholtzSpectrum}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}, "helmholtz": {part: HelmholtzSpectrum}, "objects": {part: Objects}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -375,6 +390,11 @@ class WassersteinGAN:
             if part not in z:
                 z[part] = self._helmholtz_acc(fine)
             kw["helmholtz"] = z[part]
+        if self.log_objects:
+            b = acc.setdefault("objects", {})
+            if part not in b:
+                b[part] = self._objects_acc(fine)
+            kw["objects"] = b[part]
         return kw
 
     def _helmholtz_summary(self, acc):
@@ -439,6 +459,13 @@ class WassersteinGAN:
         Joint is kept in ``joint_results``."""
         res = acc.reduce_(self.dist).result()
         self.joint_results[part] = res
+        return res.summary()
+
+    def _objects_summary(self, part, acc):
+        """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the
+        ObjectsResult is kept in ``objects_results``."""
+        res = acc.reduce_(self.dist).result()
+        self.objects_results[part] = res
         return res.summary()
 
     def _fss_summary(self, part, acc):
@@ -527,7 +554,8 @@ class WassersteinGAN:
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
         if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
-                or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal or self.log_helmholtz):
+                or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal or self.log_helmholtz
+                or self.log_objects):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -558,6 +586,9 @@ class WassersteinGAN:
                 summary["temporal"] = {k: self._temporal_summary(k, v, epoch) for k, v in acc.get("temporal", {}).items()}
             if self.log_helmholtz:
                 summary["helmholtz"] = {k: self._helmholtz_summary(v) for k, v in acc.get("helmholtz", {}).items()}
+            if self.log_objects:
+                self.objects_results = {}
+                summary["objects"] = {k: self._objects_summary(k, v) for k, v in acc.get("objects", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

@@ -84,6 +84,7 @@ FSS_MAX_THR, FSS_MAX_SCALES, FSS_MAX_SIDE = 4, 8, 2048
 HIST2D_MAX_PAIRS, HIST2D_MAX_CELLS, HIST2D_MAX_SECTORS = 8, 16384, 72
 INCR_MAX_LAGS, INCR_MAX_LAG, INCR_MAX_BINS, INCR_MAX_SIDE = 8, 256, 512, 2048
 GRIDHIST_MAX_BINS, GRIDHIST_MAX_Q = 256, 16
+OBJ_MAX_SIDE, OBJ_MAX_THR, OBJ_COLS = 2048, 4, 12
 TEMPORAL_MAX_THR, TEMPORAL_MAX_DUR, TEMPORAL_MAX_LAGS, TEMPORAL_MAX_LAG, TEMPORAL_MAX_BINS = 4, 256, 4, 24, 512
 
 
@@ -123,6 +124,12 @@ class IncrSpec(C.Structure):
     _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nlag", C.c_int), ("nbins", C.c_int),
                 ("lag", C.c_int * INCR_MAX_LAGS), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
                 ("lo", (C.c_float * INCR_MAX_LAGS) * HIST_MAX_OUT), ("inv_w", (C.c_float * INCR_MAX_LAGS) * HIST_MAX_OUT)]
+
+
+class ObjectsSpec(C.Structure):
+    _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("connectivity", C.c_int),
+                ("inv_quantum", C.c_float), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
+                ("thr", (C.c_float * OBJ_MAX_THR) * HIST_MAX_OUT)]
 
 
 class TemporalSpec(C.Structure):
@@ -234,12 +241,15 @@ _PROTOS = {
     "dg_temporal": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(TemporalSpec), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                     _vp],
     "dg_temporal_host": [C.POINTER(TemporalSpec), _vp, _i, _i, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "dg_objects_ws_bytes": [C.POINTER(EofFields), _i, _i, C.POINTER(ObjectsSpec)],
+    "dg_objects": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(ObjectsSpec), _vp, _vp, _i64, _vp, _vp, _vp],
+    "dg_objects_host": [C.POINTER(ObjectsSpec), _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp],
 }
 _RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_size_t,
              "dg_helmholtz_ws_bytes": C.c_size_t, "dg_helmholtz_cross_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
              "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t,
              "dg_incr_ws_bytes": C.c_size_t, "dg_gridhist_ws_bytes": C.c_size_t,
-             "dg_temporal_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+             "dg_temporal_ws_bytes": C.c_size_t, "dg_objects_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

@@ -1237,7 +1237,7 @@ class TrainEngine:
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
     def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None):
+                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1265,7 +1265,9 @@ class TrainEngine:
         ``temporal``: a paired ``temporal.Temporal`` that likewise receives (fine[:n], fake[:n]) in one call, as the next n times
         of its series: the caller feeds the batches in time order.
         ``helmholtz``: a ``spectra.HelmholtzSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the rotational and
-        divergent kinetic energy spectra of both wind fields and the coherence of each part."""
+        divergent kinetic energy spectra of both wind fields and the coherence of each part.
+        ``objects``: a paired ``objects.Objects`` that likewise receives (fine[:n], fake[:n]) in one call: the connected exceedance
+        objects of both series, pooled on the host (one synchronising copy of the object count per call)."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1296,6 +1298,8 @@ class TrainEngine:
             hist_maps.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if temporal is not None:
             temporal.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if objects is not None:
+            objects.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

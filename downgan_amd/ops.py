@@ -1108,6 +1108,55 @@ class HipOps:
         check(self.lib.dg_fss(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(sums), _ptr(rates),
                               _ptr(per_field), self._stream()), "dg_fss")
 
+    # ------------------------------------------------------------------ exceedance objects (csrc/objects.hip)
+    def objects_ws_bytes(self, f, H, W, spec):
+        """Workspace bytes of one dg_objects call over the descriptor ``f`` (either series) of H x W fields with the
+        _lib.ObjectsSpec ``spec`` (0: invalid, or more fields than one call may take: T 2 nout nthr ceil(P / 2) >= 2^31)."""
+        return int(self.lib.dg_objects_ws_bytes(C.byref(f), int(H), int(W), C.byref(spec)))
+
+    def objects_raw(self, fa, fb, H, W, spec, table, count, per_plane):
+        """One dg_objects call: the records of the series ``fa`` (real) and ``fb`` (generated, or None) into table int64
+        [capacity, 12] in unspecified row order, count int64 [1] = the true number of objects (also beyond the capacity, when the
+        table's content is unspecified), per_plane int64 [T 2 nout nthr] = the exact count of every plane.  The workspace is
+        cached on this object."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        cap = int(table.shape[0])
+        assert table.dtype == torch.int64 and table.is_contiguous() and table.is_cuda and table.dim() == 2 and table.shape[1] == _lib.OBJ_COLS
+        for out, m in ((count, 1), (per_plane, fa.T * 2 * nout * spec.nthr)):
+            assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == m and out.is_cuda, (m,)
+        assert fb is None or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.objects_ws_bytes(fa, H, W, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, H, W, spec.nthr, spec.connectivity)
+        ws = getattr(self, "_objects_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._objects_ws = ws = None
+            self._objects_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_objects(C.byref(fa), C.byref(fb) if fb is not None else None, int(H), int(W), C.byref(spec), _ptr(ws),
+                                  _ptr(table) if cap else None, cap, _ptr(count), _ptr(per_plane), self._stream()), "dg_objects")
+
+    def objects(self, fa, fb, H, W, spec, capacity=None):
+        """(table int64 [count, 12] SORTED by (plane, root), per_plane int64 [T 2 nout nthr], calls) of the series ``fa``, ``fb``
+        (None: one series).  The table starts at ``capacity`` rows (default: the last call's, at least 1024) and, when the true
+        count (one synchronising copy per call) exceeds it, is grown to the count and the call repeated; the key plane P + root is
+        sorted on the device (torch.sort)."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        cap = max(1024, getattr(self, "_objects_cap", 0)) if capacity is None else int(capacity)
+        count = torch.empty(1, dtype=torch.int64, device=self.device)
+        per_plane = torch.empty(fa.T * 2 * nout * spec.nthr, dtype=torch.int64, device=self.device)
+        calls = 0
+        while True:
+            table = torch.empty(cap, _lib.OBJ_COLS, dtype=torch.int64, device=self.device)
+            self.objects_raw(fa, fb, H, W, spec, table, count, per_plane)
+            calls += 1
+            n = int(count.item())
+            if n <= cap:
+                break
+            cap = n
+        self._objects_cap = max(getattr(self, "_objects_cap", 0), cap)
+        table = table[:n]
+        order = torch.sort(table[:, 0] * int(fa.P) + table[:, 1]).indices
+        return table.index_select(0, order), per_plane, calls
+
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32
         check(self.lib.dg_sum_strided(_ptr(inp), n, stride, float(scale), _ptr(out), self._stream()), "dg_sum_strided")

@@ -923,6 +923,73 @@ int dg_temporal(const dg_eof_fields* a, const dg_eof_fields* b, const dg_tempora
 int dg_temporal_host(const dg_temporal_spec* s, const float* x, int C, int T, int P, int64_t t0, int32_t* open, float* tail,
                      int64_t* spells, int32_t* spellmap, int64_t* ramps, double* acsum, int32_t* accnt);
 
+/* ---- Exceedance objects (csrc/objects.hip) ----------------------------------------------------------------------------------
+ * Every other diagnostic treats a field as a bag of pixels or of Fourier modes; this one knows that the pixels above a threshold
+ * form things: a gust front, a lee jet, a convective cell, each with an area, a mass, a peak and a place.  From the records follow
+ * object counts and size distributions, per-object hits / misses / false alarms and the SAL score (Wernli et al. 2008), all formed
+ * on the host.  Fields are H x W, read through the EOF descriptor with P = H*W, p = h*W + w; series a (real) is required, series b
+ * (generated) is optional, of equal T, C, P with its own layout and dtype (NCHW fp32 / bf16, the resident feed's [n, H, W, c] store,
+ * the generator's padded NHWC output).  The output values y are those of the value histograms and of the fractions skill score
+ * (hist_affine, hist_speed of csrc/hist_common.h): C components plus the optional speed channel appended last (nout = C + 1).
+ * For output channel j and threshold k:
+ *   mask        I[t,p] = (y > thr[j][k]), an fp32 compare: NaN is false, +inf is true, equality is false
+ *   object      a connected component of the mask; connectivity 4 joins edge neighbours, 8 adds the corner neighbours
+ *   root        the smallest linear index h*W + w among the object's pixels: the object's identity within its plane
+ *   intensity   q = clamp(rint(t), 0, 2^24 - 1), t = fp32(y * inv_quantum): one fp32 multiply, round to nearest even;
+ *               t >= 16777215.f gives 2^24 - 1, a negative t gives 0 (a NaN y is never in a mask)
+ * The RECORD of an object is one row of DG_OBJ_COLS = 12 int64:
+ *   [plane, root, area, overlap, mass, sum_qh, sum_qw, qmax, h0, h1, w0, w1]
+ *   plane     ((t*2 + side)*nout + j)*nthr + k; t the field's index within the call, side 0 = a (real), 1 = b (generated)
+ *   area      the pixel count
+ *   overlap   the number of the object's pixels that are also set in the other side's mask of the same (t, j, k); 0 when b is NULL
+ *   mass      sum q;  sum_qh = sum q*h;  sum_qw = sum q*w;  qmax = max q
+ *   h0 .. w1  the bounding box, inclusive
+ * H, W <= DG_OBJ_MAX_SIDE keeps sum q*h below 2^24 * 2^11 * 2^22 = 2^57.  Everything is integer after the compare and the rounding:
+ * the records are exact, do not depend on the order of arrival, on layout or on dtype (bf16 inputs are the values read), and two
+ * calls on the same data agree in every bit (up to the order of the rows).
+ *
+ * Device algorithm (labels and slot ids are int32 planes of the workspace, 8 bytes per pixel and plane):
+ *   init     one wave per row: the masks of all (j, k) as wave ballots; a set pixel's first label is the index of the first pixel
+ *            of its horizontal run (from the ballot, with a wave-uniform carry across 64-pixel chunks), a clear pixel's is -1
+ *   merge    lock-free union-find: a set pixel joins its run with the set neighbours of the row above (N; NW and NE for 8) --
+ *            find both roots, atomicMin the smaller into the larger root's label, continue from the value the atomic returns
+ *   flatten  label[p] = find(p); links only ever point to smaller member indices, so the root is the smallest index
+ *   slots    every root draws a record slot from a counter (one atomic per wave), bumps per_plane, writes plane / root and the
+ *            initial record and stores its slot id in the second int32 plane; slots at or beyond capacity are counted only
+ *   stats    every set pixel adds to its object's record with 64-bit integer atomics (add, min, max); consecutive lanes of a
+ *            wave that share a root combine first, so a row segment of an object costs one set of atomics per 64 pixels
+ * No lane, wave or workgroup ever waits for a value another one writes; every loop of find and union walks strictly decreasing
+ * indices and carries a hard cap of P steps, at which it sets an error word and leaves: dg_objects then returns DG_ERR_LAUNCH.
+ *
+ * dg_objects_ws_bytes: workspace bytes of one call, sized for both sides (0 for an invalid descriptor, grid or spec, or when
+ *   T*2*nout*nthr * ceil(P/2), the most objects a call can hold, reaches 2^31: cut the fields into more calls).
+ * dg_objects: count (device int64[1]) receives the true number of objects of the call, also when it exceeds capacity; per_plane
+ *   (device int64 [T*2*nout*nthr]) receives the exact object count of every plane, always (the side-1 entries are zero when b is
+ *   NULL); table is int64 [capacity][12] and holds every record when count <= capacity, in unspecified row order ((plane, root) is
+ *   a unique key); its content is unspecified when count > capacity, and nothing is written past capacity rows.  The call waits
+ *   for the stream once, to read the error word.  Rejected before any launch (DG_ERR_BAD_SHAPE; DG_ERR_BAD_DTYPE for a dtype
+ *   other than fp32 / bf16): a NULL pointer that is needed (table may be NULL when capacity is 0), descriptors that differ in
+ *   T, C or P, P != H*W, a side above DG_OBJ_MAX_SIDE, connectivity not 4 or 8, nthr outside 1 .. DG_OBJ_MAX_THR, a non-finite
+ *   thr, scale, offset or inv_quantum, inv_quantum <= 0, speed channels that do not exist, capacity < 0.
+ * dg_objects_host: host-side, the same definition for one field (b NULL) or one field pair, planar fp32 [C][H][W], by a plain
+ *   flood fill; t = 0 in plane; rows sorted by (plane, root); count, per_plane ([2*nout*nthr]) and capacity as above. */
+#define DG_OBJ_MAX_SIDE 2048
+#define DG_OBJ_MAX_THR 4
+#define DG_OBJ_COLS 12
+typedef struct dg_objects_spec {
+  int speed_u, speed_v;                 /* input channels of the speed channel, or -1, -1: none */
+  int nthr;                             /* 1 .. DG_OBJ_MAX_THR */
+  int connectivity;                     /* 4 or 8 */
+  float inv_quantum;                    /* finite, > 0: q = rint(y * inv_quantum) */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float thr[DG_HIST_MAX_OUT][DG_OBJ_MAX_THR];        /* per output channel, the first nthr finite */
+} dg_objects_spec;
+size_t dg_objects_ws_bytes(const dg_eof_fields* a, int H, int W, const dg_objects_spec* s);
+int dg_objects(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_objects_spec* s, void* ws, int64_t* table,
+               int64_t capacity, int64_t* count, int64_t* per_plane, void* stream);
+int dg_objects_host(const dg_objects_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* table, int64_t capacity,
+                    int64_t* count, int64_t* per_plane);
+
 #ifdef __cplusplus
 }
 #endif
