@@ -148,7 +148,8 @@ class WassersteinGAN:
         return float(e._sc("gp_ret").item())
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                                  coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None):
+                                  coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None,
+                                  distances=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
         pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
@@ -159,7 +160,8 @@ class WassersteinGAN:
         same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given); ``temporal``: one
         paired ``temporal.Temporal`` fed the same pair as the next times of its series (likewise only when given); ``helmholtz``:
         one ``spectra.HelmholtzSpectrum`` fed the same pair (likewise only when given); ``objects``: one paired
-        ``objects.Objects`` fed the same pair (likewise only when given)."""
+        ``objects.Objects`` fed the same pair (likewise only when given); ``distances``: one ``distmap.Distances`` fed the same
+        pair (likewise only when given)."""
         more = {} if hist_maps is None else {"hist_maps": hist_maps}
         if temporal is not None:
             more["temporal"] = temporal
@@ -167,6 +169,8 @@ class WassersteinGAN:
             more["helmholtz"] = helmholtz
         if objects is not None:
             more["objects"] = objects
+        if distances is not None:
+            more["distances"] = distances
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -263,6 +267,13 @@ class WassersteinGAN:
     log_objects = False
     objects_spec = None
     objects_results = None       # the last epoch's {"train" / "test": objects.ObjectsResult} when logged
+    # opt-in: distance-map verification of the same (real, generated) pairs -- the exact distance transforms of the exceedance
+    # masks per threshold (mean error distance in both directions, Hausdorff distance, Baddeley's Delta, displacement quantiles),
+    # reported per epoch in summary["distances"]; distance_spec None = distmap.DistSpec.zscore(n_predictands).  Every metrics
+    # pass then waits once for its records
+    log_distances = False
+    distance_spec = None
+    distance_results = None      # the last epoch's {"train" / "test": distmap.DistanceResult} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -324,6 +335,12 @@ class WassersteinGAN:
         dev = self._engine.ops.device if self._engine is not None else self.G.device
         return Objects(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
 
+    def _distances_acc(self, fine):
+        from ..distmap import Distances, DistSpec
+        spec = self.distance_spec if self.distance_spec is not None else DistSpec.zscore(self.G.n_predictands)
+        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        return Distances(spec, fine.shape[-2], fine.shape[-1], device=dev)
+
     def _coherence_acc(self, fine):
         from ..spectra import CrossSpectrum
         dev = self._engine.ops.device if self._engine is not None else self.G.device
@@ -337,7 +354,7 @@ class WassersteinGAN:
 
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}, "helmholtz": {part: HelmholtzSpectrum}, "objects": {part: Objects}}), created on first
+        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}, "helmholtz": {part: HelmholtzSpectrum}, "objects": {part: Objects}, "distances": {part: Distances}}), created on first
         use; {} when none is on."""
         kw = {}
         if self.log_spectra:
@@ -395,6 +412,11 @@ class WassersteinGAN:
             if part not in b:
                 b[part] = self._objects_acc(fine)
             kw["objects"] = b[part]
+        if self.log_distances:
+            d = acc.setdefault("distances", {})
+            if part not in d:
+                d[part] = self._distances_acc(fine)
+            kw["distances"] = d[part]
         return kw
 
     def _helmholtz_summary(self, acc):
@@ -466,6 +488,13 @@ class WassersteinGAN:
         ObjectsResult is kept in ``objects_results``."""
         res = acc.reduce_(self.dist).result()
         self.objects_results[part] = res
+        return res.summary()
+
+    def _distances_summary(self, part, acc):
+        """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the
+        DistanceResult is kept in ``distance_results``."""
+        res = acc.reduce_(self.dist).result()
+        self.distance_results[part] = res
         return res.summary()
 
     def _fss_summary(self, part, acc):
@@ -555,7 +584,7 @@ class WassersteinGAN:
                 summary["test_batches"] = len(test_metrics)
         if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
                 or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal or self.log_helmholtz
-                or self.log_objects):
+                or self.log_objects or self.log_distances):
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
@@ -589,6 +618,9 @@ class WassersteinGAN:
             if self.log_objects:
                 self.objects_results = {}
                 summary["objects"] = {k: self._objects_summary(k, v) for k, v in acc.get("objects", {}).items()}
+            if self.log_distances:
+                self.distance_results = {}
+                summary["distances"] = {k: self._distances_summary(k, v) for k, v in acc.get("distances", {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178

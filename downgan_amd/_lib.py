@@ -85,6 +85,7 @@ HIST2D_MAX_PAIRS, HIST2D_MAX_CELLS, HIST2D_MAX_SECTORS = 8, 16384, 72
 INCR_MAX_LAGS, INCR_MAX_LAG, INCR_MAX_BINS, INCR_MAX_SIDE = 8, 256, 512, 2048
 GRIDHIST_MAX_BINS, GRIDHIST_MAX_Q = 256, 16
 OBJ_MAX_SIDE, OBJ_MAX_THR, OBJ_COLS = 2048, 4, 12
+DIST_MAX_SIDE, DIST_MAX_THR, DIST_MAX_RINGS, DIST_MAX_CUTOFF, DIST_COLS, DIST_FAR = 2048, 4, 128, 512, 11, 1 << 30
 TEMPORAL_MAX_THR, TEMPORAL_MAX_DUR, TEMPORAL_MAX_LAGS, TEMPORAL_MAX_LAG, TEMPORAL_MAX_BINS = 4, 256, 4, 24, 512
 
 
@@ -130,6 +131,12 @@ class ObjectsSpec(C.Structure):
     _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("connectivity", C.c_int),
                 ("inv_quantum", C.c_float), ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
                 ("thr", (C.c_float * OBJ_MAX_THR) * HIST_MAX_OUT)]
+
+
+class DistmapSpec(C.Structure):
+    _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("nring", C.c_int), ("cutoff", C.c_int),
+                ("scale", C.c_float * EOF_MAX_C), ("offset", C.c_float * EOF_MAX_C),
+                ("thr", (C.c_float * DIST_MAX_THR) * HIST_MAX_OUT)]
 
 
 class TemporalSpec(C.Structure):
@@ -244,12 +251,17 @@ _PROTOS = {
     "dg_objects_ws_bytes": [C.POINTER(EofFields), _i, _i, C.POINTER(ObjectsSpec)],
     "dg_objects": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(ObjectsSpec), _vp, _vp, _i64, _vp, _vp, _vp],
     "dg_objects_host": [C.POINTER(ObjectsSpec), _vp, _vp, _i, _i, _i, _vp, _i64, _vp, _vp],
+    "dg_distmap_ws_bytes": [C.POINTER(EofFields), _i, _i, C.POINTER(DistmapSpec)],
+    "dg_distmap": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(DistmapSpec), _vp, _vp, _vp, _vp, _vp],
+    "dg_distmap_host": [C.POINTER(DistmapSpec), _vp, _vp, _i, _i, _i, _vp, _vp, _vp],
+    "dg_distmap_host_scalars": [C.c_int32, _i, _vp, _vp, _vp],
 }
 _RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_size_t,
              "dg_helmholtz_ws_bytes": C.c_size_t, "dg_helmholtz_cross_ws_bytes": C.c_size_t, "dg_hist_ws_bytes": C.c_size_t, "dg_gridstats_ws_bytes": C.c_size_t,
              "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t,
              "dg_incr_ws_bytes": C.c_size_t, "dg_gridhist_ws_bytes": C.c_size_t,
-             "dg_temporal_ws_bytes": C.c_size_t, "dg_objects_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
+             "dg_temporal_ws_bytes": C.c_size_t, "dg_objects_ws_bytes": C.c_size_t,
+             "dg_distmap_ws_bytes": C.c_size_t}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

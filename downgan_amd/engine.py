@@ -1237,7 +1237,7 @@ class TrainEngine:
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
     def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None):
+                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None, distances=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1267,7 +1267,9 @@ class TrainEngine:
         ``helmholtz``: a ``spectra.HelmholtzSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the rotational and
         divergent kinetic energy spectra of both wind fields and the coherence of each part.
         ``objects``: a paired ``objects.Objects`` that likewise receives (fine[:n], fake[:n]) in one call: the connected exceedance
-        objects of both series, pooled on the host (one synchronising copy of the object count per call)."""
+        objects of both series, pooled on the host (one synchronising copy of the object count per call).
+        ``distances``: a ``distmap.Distances`` that likewise receives (fine[:n], fake[:n]) in one call: the distance transforms of
+        both masks and the distance measures of the pair, pooled on the host (one synchronising copy of the records per call)."""
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1300,6 +1302,8 @@ class TrainEngine:
             temporal.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         if objects is not None:
             objects.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        if distances is not None:
+            distances.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)

@@ -1157,6 +1157,32 @@ class HipOps:
         order = torch.sort(table[:, 0] * int(fa.P) + table[:, 1]).indices
         return table.index_select(0, order), per_plane, calls
 
+    # ------------------------------------------------------------------ distance maps (csrc/distmap.hip)
+    def distmap_ws_bytes(self, f, H, W, spec):
+        """Workspace bytes of one dg_distmap call over the descriptor ``f`` (either series) of H x W fields with the
+        _lib.DistmapSpec ``spec`` (0: invalid)."""
+        return int(self.lib.dg_distmap_ws_bytes(C.byref(f), int(H), int(W), C.byref(spec)))
+
+    def distmap(self, fa, fb, H, W, spec, records=None, rings=None, d2=None):
+        """One dg_distmap call over the series ``fa`` (real) and ``fb`` (generated; None: the distance transform of ``fa``
+        alone, into ``d2``): records int64 [T, nout, nthr, 11] overwritten, rings int64 [nout, nthr, 2, nring + 2] +=, d2 int32
+        [T, 2, nout, nthr, P] (rows: include/downgan_hip.h), each optional.  Asynchronous; the workspace is cached on this
+        object."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        njk = nout * spec.nthr
+        for out, m, dt in ((records, fa.T * njk * _lib.DIST_COLS, torch.int64), (rings, njk * 2 * (spec.nring + 2), torch.int64),
+                           (d2, fa.T * 2 * njk * fa.P, torch.int32)):
+            assert out is None or (out.dtype == dt and out.is_contiguous() and out.numel() == m and out.is_cuda), (m,)
+        assert fb is None or (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.distmap_ws_bytes(fa, H, W, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, H, W, spec.nthr, spec.nring, spec.cutoff)
+        ws = getattr(self, "_distmap_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._distmap_ws = ws = None
+            self._distmap_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_distmap(C.byref(fa), C.byref(fb) if fb is not None else None, int(H), int(W), C.byref(spec), _ptr(ws),
+                                  _ptr(records), _ptr(rings), _ptr(d2), self._stream()), "dg_distmap")
+
     def sum_strided(self, inp, n, stride, scale, out):
         assert inp.dtype == torch.float32 and out.dtype == torch.float32
         check(self.lib.dg_sum_strided(_ptr(inp), n, stride, float(scale), _ptr(out), self._stream()), "dg_sum_strided")

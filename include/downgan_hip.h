@@ -990,6 +990,73 @@ int dg_objects(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, con
 int dg_objects_host(const dg_objects_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* table, int64_t capacity,
                     int64_t* count, int64_t* per_plane);
 
+/* ---- Distance maps (csrc/distmap.hip) ---------------------------------------------------------------------------------------
+ * How far from a real exceedance does the generator put its exceedances, in pixels?  The exact Euclidean distance transform (EDT)
+ * of the exceedance masks, and from it the distance measures of binary fields: the mean error distance (MED) in both directions
+ * (generated -> real: false alarms; real -> generated: misses), the Hausdorff distance, the ring counts behind the partial
+ * Hausdorff distance, and the sums of Baddeley's Delta.  Fields, layouts, dtypes, the output values y and the masks
+ * y > thr[j][k] (NaN never set) are those of the exceedance objects above; side 0 = a (real, mask A), side 1 = b (generated, B).
+ *   d2(x)     int32: the squared Euclidean distance in pixels from x to the nearest set pixel of the plane; 0 on the mask;
+ *             DG_DIST_FAR = 2^30 everywhere when the mask is empty
+ *   ring(d2)  the smallest integer r with d2 <= r*r (the distance rounded up), in integers
+ *   dq(d2)    floor(sqrt(d2 * 2^20)): the distance in units of 2^-10 px, exact in 64-bit integers (a sqrt is a first guess only,
+ *             corrected by integer multiplies); dq(25) = 5120
+ *   w(x)      min(dq(d2(x)), cutoff * 1024), and cutoff * 1024 where d2 is FAR; cutoff in 1 .. DG_DIST_MAX_CUTOFF pixels
+ * The RECORD of a field pair (t, j, k) is one row of DG_DIST_COLS = 11 int64:
+ *   [n_a, n_b, n_ab, sum_dq_b2a, sum_d2_b2a, max_d2_b2a, sum_dq_a2b, sum_d2_a2b, max_d2_a2b, bad1, bad2]
+ *   n_a, n_b, n_ab   pixels in A, in B, in both
+ *   *_b2a            sum / max over x in B of dq(d2_A(x)), d2_A(x);  *_a2b: over x in A of dq(d2_B(x)), d2_B(x)
+ *   bad1, bad2       sum over ALL pixels of |w_A - w_B| and of (w_A - w_B)^2
+ * Columns 3 .. 8 are all -1 unless n_a > 0 and n_b > 0; bad1 and bad2 are always defined.  With H, W <= DG_DIST_MAX_SIDE and
+ * cutoff <= 512, bad2 <= 2^22 * 2^38 = 2^60 and the other sums stay below 2^45: a record cannot overflow (records are per field
+ * and never summed on the device).
+ * The RING TABLE is int64 [nout][nthr][2][nring + 2], accumulated (the caller zeroes it): direction 0 counts the pixels of B by
+ * ring(d2_A), direction 1 the pixels of A by ring(d2_B); bin r < nring holds ring r (bin 0: the overlap), bin nring the pixels
+ * with ring >= nring, bin nring + 1 the pixels of a field whose other side is empty.
+ * Everything is integer after the compare: results are exact, do not depend on the order of arrival, on layout or on dtype (bf16
+ * inputs are the values read), and agree in every bit from run to run.
+ *
+ * Device algorithm (the workspace holds one uint16 per plane pixel and nothing else):
+ *   columns   one thread per column of a (t, side): down the column, g = the distance to the nearest set pixel above (0xFFFF:
+ *             none), for all (j, k) at once; then one thread per column of a plane: up, g lowered to the distance to the nearest
+ *             set pixel below
+ *   rows      one workgroup per row of a (t, j, k), both sides: g^2 in LDS; each pixel scans outward, best = min(best, D^2 +
+ *             g^2[w +- D]) while D^2 < best -- exact, since no candidate with D^2 >= best can win; a row without a finite g
+ *             belongs to an empty plane and is not scanned; ring, dq and w of both sides; wave reductions, one set of 64-bit
+ *             integer atomics per wave into the record, the ring bins through an LDS table
+ *   finalize  one thread per record writes the -1 columns
+ *
+ * dg_distmap_ws_bytes: workspace bytes of one call, sized for both sides: T*2*nout*nthr*P*2 (0 for anything invalid).
+ * dg_distmap: records int64 [T][nout][nthr][11], overwritten, may be NULL; rings accumulates, may be NULL; d2 int32
+ *   [T][2][nout][nthr][P], may be NULL.  When b is NULL (one series: the EDT alone) d2 must be given, records and rings must be
+ *   NULL, and the side-1 planes of d2 are left untouched.  Asynchronous on the stream.  Rejected before any launch
+ *   (DG_ERR_BAD_ARG; DG_ERR_BAD_DTYPE for a dtype other than fp32 / bf16): a NULL pointer that is needed, descriptors that differ
+ *   in T, C or P, P != H*W, a side above DG_DIST_MAX_SIDE, nthr, nring or cutoff out of range, a non-finite thr, scale or offset,
+ *   speed channels that do not exist, nothing to compute (b given and records, rings, d2 all NULL).
+ * dg_distmap_host: host-side, the same definition for one field (b NULL) or one field pair, planar fp32 [C][H][W], in plain C++:
+ *   records [nout][nthr][11], rings as above (accumulated), d2 [2][nout][nthr][P]; the same rules for NULL.
+ * dg_distmap_host_scalars: host-side, ring, dq and w of one d2 in 0 .. DG_DIST_FAR: the integer definitions above on their own. */
+#define DG_DIST_MAX_SIDE 2048
+#define DG_DIST_MAX_THR 4
+#define DG_DIST_MAX_RINGS 128
+#define DG_DIST_MAX_CUTOFF 512
+#define DG_DIST_COLS 11
+#define DG_DIST_FAR (1 << 30)
+typedef struct dg_distmap_spec {
+  int speed_u, speed_v;                 /* input channels of the speed channel, or -1, -1: none */
+  int nthr;                             /* 1 .. DG_DIST_MAX_THR */
+  int nring;                            /* 1 .. DG_DIST_MAX_RINGS */
+  int cutoff;                           /* 1 .. DG_DIST_MAX_CUTOFF pixels: the cap of Baddeley's w */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float thr[DG_HIST_MAX_OUT][DG_DIST_MAX_THR];       /* per output channel, the first nthr finite */
+} dg_distmap_spec;
+size_t dg_distmap_ws_bytes(const dg_eof_fields* a, int H, int W, const dg_distmap_spec* s);
+int dg_distmap(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_distmap_spec* s, void* ws, int64_t* records,
+               int64_t* rings, int32_t* d2, void* stream);
+int dg_distmap_host(const dg_distmap_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* records, int64_t* rings,
+                    int32_t* d2);
+int dg_distmap_host_scalars(int32_t d2, int cutoff, int32_t* ring, int64_t* dq, int64_t* w);
+
 #ifdef __cplusplus
 }
 #endif
