@@ -30,7 +30,7 @@ constexpr int ROW_THREADS = 256;
 constexpr int DOWN_ROWS = 4, UP_ROWS = 8;             // rows whose loads a column thread issues before it uses them
 constexpr int DIST_GRID_PLANES = 16384;               // planes across gridDim.y at most; the up kernel strides over the rest
 constexpr int DIST_GRID_T = 4096;                     // fields across gridDim.y at most; the kernels stride over the rest
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXK = DG_DIST_MAX_THR, COLS = DG_DIST_COLS;
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXK = DG_DIST_MAX_THR, COLS = DG_DIST_COLS;
 constexpr int FAR = DG_DIST_FAR;
 constexpr int NONE = 0xFFFF;                          // g of a column without a set pixel
 constexpr int MAXBINS = DG_DIST_MAX_RINGS + 2;
@@ -55,45 +55,12 @@ __host__ __device__ inline long long dist_dq(int d2) {
 }
 
 struct DistColArgs {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-  int C, H, W, T, nout, speed, su, sv, nthr, side;
-  float scale[MAXC], offset[MAXC], thr[MAXO][MAXK];
+  HistSeries x;
+  HistXform xf;
+  int H, W, T, nout, nthr, side;
+  float thr[MAXO][MAXK];
   unsigned short* g;          // plane ((t * 2 + side) * nout + j) * nthr + k, H * W entries each
 };
-
-// the nout output values of one pixel (q: its channel 0), as obj_values of objects.hip
-template <typename T, int MODE>
-__device__ __forceinline__ void dist_values(const DistColArgs& g, const T* q, float (&y)[MAXO]) {
-  float v[MAXC];
-  if (MODE == HIST_PIX16) {
-    const uint4 r = *reinterpret_cast<const uint4*>(q);
-    const unsigned u[4] = {r.x, r.y, r.z, r.w};
-    if (sizeof(T) == 2) {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[c] = __uint_as_float(c & 1 ? u[c / 2] & 0xffff0000u : u[c / 2] << 16);
-    } else {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[c] = c < 4 ? __uint_as_float(u[c & 3]) : 0.f;
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) v[c] = c < g.C ? ld_elem(q + c * g.ld_c) : 0.f;
-  }
-  float yu = 0.f, yv = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    y[c] = hist_affine(v[c], g.scale[c], g.offset[c]);
-    yu = c == g.su ? y[c] : yu;
-    yv = c == g.sv ? y[c] : yv;
-  }
-  y[MAXO - 1] = 0.f;
-  if (g.speed) {
-    const float s = hist_speed(yu, yv);
-#pragma unroll
-    for (int j = 0; j < MAXO; ++j) y[j] = j == g.C ? s : y[j];
-  }
-}
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(COL_THREADS) void dist_down_kernel(DistColArgs g) {
@@ -101,7 +68,7 @@ __global__ __launch_bounds__(COL_THREADS) void dist_down_kernel(DistColArgs g) {
   if (w >= g.W) return;
   const long long P = (long long)g.H * g.W;
   const int njk = g.nout * g.nthr;
-  const T* base = reinterpret_cast<const T*>(g.base);
+  const T* base = reinterpret_cast<const T*>(g.x.base);
   for (int t = blockIdx.y; t < g.T; t += gridDim.y) {
     unsigned short* G = g.g + ((long long)t * 2 + g.side) * njk * P + w;
     int last[MAXO][MAXK];                                            // the last set row of every (j, k) so far, or -1
@@ -114,7 +81,7 @@ __global__ __launch_bounds__(COL_THREADS) void dist_down_kernel(DistColArgs g) {
 #pragma unroll
       for (int u = 0; u < DOWN_ROWS; ++u) {
         const int h = h0 + u < g.H ? h0 + u : g.H - 1;               // rows beyond the column read its last pixel, unused
-        dist_values<T, MODE>(g, base + t * g.ld_t + ((long long)h * g.W + w) * g.ld_p, y[u]);
+        hist_pixel_values<T, MODE>(g.xf, base + t * g.x.ld_t + ((long long)h * g.W + w) * g.x.ld_p, g.x.ld_c, y[u]);
       }
 #pragma unroll
       for (int u = 0; u < DOWN_ROWS; ++u) {
@@ -303,43 +270,27 @@ __global__ __launch_bounds__(ROW_THREADS) void dist_finalize_kernel(u64* records
     for (int c = 3; c <= 8; ++c) rec[c] = ~0ull;                     // -1
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 bool spec_ok(const dg_distmap_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC || s->nthr < 1 || s->nthr > MAXK) return false;
+  if (!s || s->nthr < 1 || s->nthr > MAXK) return false;
   if (s->nring < 1 || s->nring > DG_DIST_MAX_RINGS || s->cutoff < 1 || s->cutoff > DG_DIST_MAX_CUTOFF) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
-  for (int j = 0; j < nout; ++j)
-    for (int k = 0; k < s->nthr; ++k)
-      if (!finite_f(s->thr[j][k])) return false;
-  return true;
+  return hist_xform_ok(s, C) && hist_thr_ok(s->thr, hist_nout(s, C), s->nthr);
 }
 
 bool grid_ok(int H, int W) { return H >= 1 && W >= 1 && H <= DG_DIST_MAX_SIDE && W <= DG_DIST_MAX_SIDE; }
 
 long long planes_of(const dg_eof_fields* a, const dg_distmap_spec* s) {
-  return (long long)a->T * 2 * (a->C + (s->speed_u >= 0 ? 1 : 0)) * s->nthr;
+  return (long long)a->T * 2 * hist_nout(s, a->C) * s->nthr;
 }
 
 bool call_ok(const dg_eof_fields* a, int H, int W, const dg_distmap_spec* s) {
   return hist_fields_ok(a) && spec_ok(s, a->C) && grid_ok(H, W) && (long long)H * W == a->P;
 }
 
-template <typename T>
-void launch_cols(int mode, const DistColArgs& g, dim3 grid, hipStream_t st) {
-  if (mode == HIST_PIX16) hipLaunchKernelGGL((dist_down_kernel<T, HIST_PIX16>), grid, dim3(COL_THREADS), 0, st, g);
-  else hipLaunchKernelGGL((dist_down_kernel<T, HIST_ANY>), grid, dim3(COL_THREADS), 0, st, g);
-}
-
 void cols_of(const dg_eof_fields* x, int side, DistColArgs g, dim3 grid, hipStream_t st) {
-  g.base = x->base; g.ld_t = x->ld_t; g.ld_c = x->ld_c; g.ld_p = x->ld_p; g.side = side;
-  const int mode = hist_mode(x);
-  if (x->dtype == DG_BF16) launch_cols<bf16_t>(mode, g, grid, st);
-  else launch_cols<float>(mode, g, grid, st);
+  g.x = hist_series(x); g.side = side;
+  hist_dispatch<false>(x->dtype, hist_mode(x), [&](auto t, auto m) {
+    hipLaunchKernelGGL((dist_down_kernel<decltype(t), decltype(m)::value>), grid, dim3(COL_THREADS), 0, st, g);
+  });
 }
 
 // Host reference.  hd[r * W + w]: the distance within row r from w to the nearest set pixel of that row (BIG: the row has none).
@@ -398,8 +349,7 @@ extern "C" int dg_distmap_host(const dg_distmap_spec* s, const float* a, const f
                                int64_t* rings, int32_t* d2) {
   if (!spec_ok(s, C) || !a || !grid_ok(H, W)) return DG_ERR_BAD_ARG;
   if (b ? (!records && !rings && !d2) : (!d2 || records || rings)) return DG_ERR_BAD_ARG;
-  const bool speed = s->speed_u >= 0;
-  const int nout = C + (speed ? 1 : 0), nb = s->nring + 2;
+  const int nout = hist_nout(s, C), nb = s->nring + 2;
   const size_t P = (size_t)H * W;
   const long long cap = (long long)s->cutoff * 1024;
   const float* x[2] = {a, b};
@@ -411,15 +361,7 @@ extern "C" int dg_distmap_host(const dg_distmap_spec* s, const float* a, const f
     for (int k = 0; k < s->nthr; ++k) {
       long long n[2] = {0, 0};
       for (int e = 0; e < (b ? 2 : 1); ++e) {
-        for (size_t p = 0; p < P; ++p) {
-          if (j < C) {
-            y[p] = hist_affine(x[e][j * P + p], s->scale[j], s->offset[j]);
-          } else {
-            const int u = s->speed_u, v = s->speed_v;
-            y[p] = hist_speed(hist_affine(x[e][u * P + p], s->scale[u], s->offset[u]),
-                              hist_affine(x[e][v * P + p], s->scale[v], s->offset[v]));
-          }
-        }
+        for (size_t p = 0; p < P; ++p) y[p] = hist_host_value(s, x[e], C, P, p, j);
         mask[e].assign(P, 0);
         for (size_t p = 0; p < P; ++p) {
           mask[e][p] = y[p] > s->thr[j][k] ? 1 : 0;
@@ -474,19 +416,14 @@ extern "C" int dg_distmap(const dg_eof_fields* a, const dg_eof_fields* b, int H,
   if (b ? (!records && !rings && !d2) : (!d2 || records || rings)) return DG_ERR_BAD_ARG;
   if ((a->dtype != DG_F32 && a->dtype != DG_BF16) || (b && b->dtype != DG_F32 && b->dtype != DG_BF16)) return DG_ERR_BAD_DTYPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int nout = a->C + (s->speed_u >= 0 ? 1 : 0), njk = nout * s->nthr;
+  const int nout = hist_nout(s, a->C), njk = nout * s->nthr;
   const long long nrec = (long long)a->T * njk;
   if (records && hipMemsetAsync(records, 0, (size_t)nrec * COLS * sizeof(int64_t), st) != hipSuccess) return DG_ERR_LAUNCH;
 
   DistColArgs g;
-  g.C = a->C; g.H = H; g.W = W; g.T = a->T; g.nout = nout; g.nthr = s->nthr;
-  g.speed = s->speed_u >= 0 ? 1 : 0; g.su = g.speed ? s->speed_u : -1; g.sv = g.speed ? s->speed_v : -1;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < a->C ? s->scale[c] : 1.f;
-    g.offset[c] = c < a->C ? s->offset[c] : 0.f;
-  }
-  for (int j = 0; j < MAXO; ++j)
-    for (int k = 0; k < MAXK; ++k) g.thr[j][k] = j < nout && k < s->nthr ? s->thr[j][k] : INFINITY;
+  g.xf = hist_xform(s, a->C);
+  g.H = H; g.W = W; g.T = a->T; g.nout = nout; g.nthr = s->nthr;
+  hist_thr_pad(s->thr, nout, s->nthr, g.thr);
   g.g = reinterpret_cast<unsigned short*>(ws);
   const unsigned gt = (unsigned)(a->T < DIST_GRID_T ? a->T : DIST_GRID_T);
   const dim3 cgrid((unsigned)((W + COL_THREADS - 1) / COL_THREADS), gt);

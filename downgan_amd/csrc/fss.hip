@@ -29,16 +29,16 @@ constexpr int FSS_WAVES = FSS_THREADS / 64;
 constexpr int FSS_PIX_PER_WG = 1024;                  // 4 pixels per thread: 1024 c^2 <= 2^54 per workgroup sum
 constexpr int FSS_GRID_T = 4096;                      // fields across gridDim.y at most; the kernels stride over the rest
 constexpr int FSS_COLS_GRID_MAX = 1 << 20;
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXK = DG_FSS_MAX_THR, MAXS = DG_FSS_MAX_SCALES;
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXK = DG_FSS_MAX_THR, MAXS = DG_FSS_MAX_SCALES;
 constexpr long long FSS_LIMIT = 1LL << 62;
 
 typedef unsigned long long u64;
 
 struct FssRowArgs {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-  int C, H, W, T, nout, speed, su, sv, nthr, side;
-  float scale[MAXC], offset[MAXC], thr[MAXO][MAXK];
+  HistSeries x;
+  HistXform xf;
+  int H, W, T, nout, nthr, side;
+  float thr[MAXO][MAXK];
   unsigned* planes;           // plane ((t * 2 + side) * nout + j) * nthr + k, H * W entries each
 };
 
@@ -49,46 +49,13 @@ struct FssWinArgs {
   int r[MAXS];
 };
 
-// the nout output values of one pixel (q: its channel 0)
-template <typename T, int MODE>
-__device__ __forceinline__ void fss_values(const FssRowArgs& g, const T* q, float (&y)[MAXO]) {
-  float v[MAXC];
-  if (MODE == HIST_PIX16) {
-    const uint4 r = *reinterpret_cast<const uint4*>(q);
-    const unsigned u[4] = {r.x, r.y, r.z, r.w};
-    if (sizeof(T) == 2) {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[c] = __uint_as_float(c & 1 ? u[c / 2] & 0xffff0000u : u[c / 2] << 16);
-    } else {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[c] = c < 4 ? __uint_as_float(u[c & 3]) : 0.f;
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) v[c] = c < g.C ? ld_elem(q + c * g.ld_c) : 0.f;
-  }
-  float yu = 0.f, yv = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    y[c] = hist_affine(v[c], g.scale[c], g.offset[c]);
-    yu = c == g.su ? y[c] : yu;
-    yv = c == g.sv ? y[c] : yv;
-  }
-  y[MAXO - 1] = 0.f;
-  if (g.speed) {
-    const float s = hist_speed(yu, yv);
-#pragma unroll
-    for (int j = 0; j < MAXO; ++j) y[j] = j == g.C ? s : y[j];
-  }
-}
-
 template <typename T, int MODE>
 __global__ __launch_bounds__(FSS_THREADS) void fss_rows_kernel(FssRowArgs g) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int h = blockIdx.x * FSS_WAVES + wave;
   if (h >= g.H) return;                                              // wave-uniform
   const long long P = (long long)g.H * g.W;
-  const T* base = reinterpret_cast<const T*>(g.base);
+  const T* base = reinterpret_cast<const T*>(g.x.base);
   const u64 upto = ~0ull >> (63 - lane);                             // lanes 0 .. lane
   for (int t = blockIdx.y; t < g.T; t += gridDim.y) {
     unsigned carry[MAXO][MAXK];
@@ -102,7 +69,7 @@ __global__ __launch_bounds__(FSS_THREADS) void fss_rows_kernel(FssRowArgs g) {
       const bool in = w < g.W;
       const long long p = (long long)h * g.W + (in ? w : g.W - 1);   // lanes beyond the row read its last pixel, unused
       float y[MAXO];
-      fss_values<T, MODE>(g, base + t * g.ld_t + p * g.ld_p, y);
+      hist_pixel_values<T, MODE>(g.xf, base + t * g.x.ld_t + p * g.x.ld_p, g.x.ld_c, y);
 #pragma unroll
       for (int j = 0; j < MAXO; ++j) {
         if (j < g.nout) {
@@ -234,18 +201,9 @@ __global__ __launch_bounds__(FSS_THREADS) void fss_finish_kernel(const u64* slot
   }
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 bool spec_ok(const dg_fss_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC || s->nthr < 1 || s->nthr > MAXK || s->nscale < 1 || s->nscale > MAXS) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
-  for (int j = 0; j < nout; ++j)
-    for (int k = 0; k < s->nthr; ++k)
-      if (!finite_f(s->thr[j][k])) return false;
+  if (!s || s->nthr < 1 || s->nthr > MAXK || s->nscale < 1 || s->nscale > MAXS) return false;
+  if (!hist_xform_ok(s, C) || !hist_thr_ok(s->thr, hist_nout(s, C), s->nthr)) return false;
   for (int i = 0; i < s->nscale; ++i) {
     const int n = s->win[i];
     if (n < 1 || n > 2 * DG_FSS_MAX_SIDE - 1 || n % 2 == 0 || (i > 0 && n <= s->win[i - 1])) return false;
@@ -271,8 +229,6 @@ long long max_bound(int H, int W, const dg_fss_spec* s) {
   return m;
 }
 
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
 struct Layout {
   int nout, njk;
   size_t slot_bytes, bytes;
@@ -280,9 +236,9 @@ struct Layout {
 
 Layout layout_of(const dg_eof_fields* a, const dg_fss_spec* s) {
   Layout l;
-  l.nout = a->C + (s->speed_u >= 0 ? 1 : 0);
+  l.nout = hist_nout(s, a->C);
   l.njk = l.nout * s->nthr;
-  l.slot_bytes = round256((size_t)a->T * l.njk * s->nscale * 3 * sizeof(u64));
+  l.slot_bytes = hist_round256((size_t)a->T * l.njk * s->nscale * 3 * sizeof(u64));
   l.bytes = l.slot_bytes + (size_t)a->T * 2 * l.njk * (size_t)a->P * sizeof(unsigned);
   return l;
 }
@@ -294,17 +250,11 @@ bool call_ok(const dg_eof_fields* a, int H, int W, const dg_fss_spec* s) {
   return mb > 0 && a->T <= FSS_LIMIT / mb;                         // T * max_s bound <= 2^62: one call cannot overflow
 }
 
-template <typename T>
-void launch_rows(int mode, const FssRowArgs& g, dim3 grid, hipStream_t st) {
-  if (mode == HIST_PIX16) hipLaunchKernelGGL((fss_rows_kernel<T, HIST_PIX16>), grid, dim3(FSS_THREADS), 0, st, g);
-  else hipLaunchKernelGGL((fss_rows_kernel<T, HIST_ANY>), grid, dim3(FSS_THREADS), 0, st, g);
-}
-
 void rows_of(const dg_eof_fields* x, int side, FssRowArgs g, dim3 grid, hipStream_t st) {
-  g.base = x->base; g.ld_t = x->ld_t; g.ld_c = x->ld_c; g.ld_p = x->ld_p; g.side = side;
-  const int mode = hist_mode(x);
-  if (x->dtype == DG_BF16) launch_rows<bf16_t>(mode, g, grid, st);
-  else launch_rows<float>(mode, g, grid, st);
+  g.x = hist_series(x); g.side = side;
+  hist_dispatch<false>(x->dtype, hist_mode(x), [&](auto t, auto m) {
+    hipLaunchKernelGGL((fss_rows_kernel<decltype(t), decltype(m)::value>), grid, dim3(FSS_THREADS), 0, st, g);
+  });
 }
 
 }  // namespace
@@ -319,8 +269,7 @@ extern "C" size_t dg_fss_ws_bytes(const dg_eof_fields* a, int H, int W, const dg
 extern "C" int dg_fss_host(const dg_fss_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* sums, int64_t* rates) {
   if (!spec_ok(s, C) || !a || !b || !sums || !rates || H < 1 || W < 1 || H > DG_FSS_MAX_SIDE || W > DG_FSS_MAX_SIDE) return DG_ERR_BAD_SHAPE;
   if (max_bound(H, W, s) == 0) return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  const int nout = C + (speed ? 1 : 0);
+  const int nout = hist_nout(s, C);
   const size_t P = (size_t)H * W, W1 = (size_t)W + 1;
   std::vector<int64_t> sat[2];                                       // (H + 1) x (W + 1), a zero row and column in front
   sat[0].assign((size_t)(H + 1) * W1, 0);
@@ -333,15 +282,7 @@ extern "C" int dg_fss_host(const dg_fss_spec* s, const float* a, const float* b,
           int64_t row = 0;
           for (int w = 0; w < W; ++w) {
             const size_t p = (size_t)h * W + w;
-            float y;
-            if (j < C) {
-              y = hist_affine(x[side][j * P + p], s->scale[j], s->offset[j]);
-            } else {
-              const int u = s->speed_u, v = s->speed_v;
-              y = hist_speed(hist_affine(x[side][u * P + p], s->scale[u], s->offset[u]),
-                             hist_affine(x[side][v * P + p], s->scale[v], s->offset[v]));
-            }
-            row += y > s->thr[j][k] ? 1 : 0;
+            row += hist_host_value(s, x[side], C, P, p, j) > s->thr[j][k] ? 1 : 0;
             sat[side][(size_t)(h + 1) * W1 + w + 1] = sat[side][(size_t)h * W1 + w + 1] + row;
           }
         }
@@ -384,14 +325,9 @@ extern "C" int dg_fss(const dg_eof_fields* a, const dg_eof_fields* b, int H, int
   if (hipMemsetAsync(slots, 0, l.slot_bytes, st) != hipSuccess) return DG_ERR_LAUNCH;
 
   FssRowArgs g;
-  g.C = a->C; g.H = H; g.W = W; g.T = a->T; g.nout = l.nout; g.nthr = s->nthr;
-  g.speed = s->speed_u >= 0 ? 1 : 0; g.su = g.speed ? s->speed_u : -1; g.sv = g.speed ? s->speed_v : -1;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < a->C ? s->scale[c] : 1.f;
-    g.offset[c] = c < a->C ? s->offset[c] : 0.f;
-  }
-  for (int j = 0; j < MAXO; ++j)
-    for (int k = 0; k < MAXK; ++k) g.thr[j][k] = j < l.nout && k < s->nthr ? s->thr[j][k] : INFINITY;
+  g.xf = hist_xform(s, a->C);
+  g.H = H; g.W = W; g.T = a->T; g.nout = l.nout; g.nthr = s->nthr;
+  hist_thr_pad(s->thr, l.nout, s->nthr, g.thr);
   g.planes = planes;
   const unsigned gt = (unsigned)(a->T < FSS_GRID_T ? a->T : FSS_GRID_T);
   const dim3 rgrid((unsigned)((H + FSS_WAVES - 1) / FSS_WAVES), gt);

@@ -27,25 +27,20 @@ constexpr int GH_THREADS = 256;
 constexpr int GH_UNROLL = 4;                          // fields in flight per series
 constexpr int GH_BLOCKS_FULL = 1024;                  // workgroups that fill the chip without cutting the fields
 constexpr int GH_SLICE_MIN_T = 8;                     // fields per slice at least: runs of equal rows stay worth combining
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXQ = DG_GRIDHIST_MAX_Q;
-
-struct GhSeries {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-};
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXQ = DG_GRIDHIST_MAX_Q;
 
 struct GhArgs {
-  GhSeries a, b;
-  int C, P, T, nout, nbins, speed, su, sv, slices;
-  float scale[MAXC], offset[MAXC], lo[MAXO], inv_w[MAXO];
+  HistSeries a, b;
+  int P, T, nout, nbins;
+  HistXform xf;
+  float lo[MAXO], inv_w[MAXO];
+  int slices;
   int* counts;
 };
 
-// what one unit of state bins: output channel j from the input channels c1 (and c2: the speed)
-struct Unit {
-  int j, c1, c2;
-  bool on, spd;
-  float sc1, of1, sc2, of2, lo, inv_w;
+// how one unit of state bins its output values
+struct Unit : HistUnit {
+  float lo, inv_w;
 };
 
 // the open run of one unit and side: `run` consecutive fields fell in `row` of the plane `base` (this thread's pixel of it)
@@ -62,56 +57,10 @@ struct Run {
   }
 };
 
-template <int MODE, int UNITS> struct Raw { float x1[UNITS], x2[UNITS]; };
-template <int UNITS> struct Raw<HIST_PIX16, UNITS> { uint4 r; };
-
-// the loads of one field of one series for the UNITS units of this thread (i: pixel quad in HIST_NCHW4, else pixel)
-template <typename T, int MODE, int UNITS, bool SPD>
-__device__ __forceinline__ void gh_load(const GhSeries& s, long long t, long long i, const Unit (&un)[UNITS], Raw<MODE, UNITS>& r) {
-  const T* base = reinterpret_cast<const T*>(s.base);
-  if constexpr (MODE == HIST_NCHW4) {
-    const T* q = base + t * s.ld_t + 4 * i;
-    ld4(q + un[0].c1 * s.ld_c, r.x1);
-    if (SPD) ld4(q + un[0].c2 * s.ld_c, r.x2);
-  } else if constexpr (MODE == HIST_PIX16) {
-    r.r = *reinterpret_cast<const uint4*>(base + t * s.ld_t + i * s.ld_p);
-  } else {
-    const T* q = base + t * s.ld_t + i * s.ld_p;
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-      r.x1[k] = ld_elem(q + un[k].c1 * s.ld_c);
-      r.x2[k] = r.x1[k];
-      if (un[k].spd) r.x2[k] = ld_elem(q + un[k].c2 * s.ld_c);       // wave-uniform
-    }
-  }
-}
-
-// channel c (wave-uniform) of the 16 bytes of one pixel: shifts of the two 64-bit halves, no register array to index
-template <typename T>
-__device__ __forceinline__ float gh_pick(const uint4& r, int c) {
-  const unsigned long long lo = ((unsigned long long)r.y << 32) | r.x, hi = ((unsigned long long)r.w << 32) | r.z;
-  if (sizeof(T) == 2) {
-    const unsigned long long q = c < 4 ? lo : hi;
-    return __uint_as_float((unsigned)(q >> (16 * (c & 3))) << 16);
-  }
-  const unsigned long long q = c < 2 ? lo : hi;                      // fp32: C <= 4 in this mode
-  return __uint_as_float((unsigned)(q >> (32 * (c & 1))));
-}
-
 // the row of unit k
 template <typename T, int MODE, int UNITS, bool SPD>
-__device__ __forceinline__ int gh_row(const Raw<MODE, UNITS>& r, const Unit& un, int k, int nbins) {
-  float x1, x2;
-  if constexpr (MODE == HIST_PIX16) {
-    x1 = gh_pick<T>(r.r, un.c1);
-    x2 = SPD ? gh_pick<T>(r.r, un.c2) : x1;
-  } else {
-    x1 = r.x1[k];
-    x2 = MODE == HIST_NCHW4 && !SPD ? x1 : r.x2[k];
-  }
-  float y = hist_affine(x1, un.sc1, un.of1);
-  if (SPD && un.spd) y = hist_speed(y, hist_affine(x2, un.sc2, un.of2));   // wave-uniform
-  return hist_bin(y, un.lo, un.inv_w, nbins);
+__device__ __forceinline__ int gh_row(const HistRaw<MODE, UNITS>& r, const Unit& un, int k, int nbins) {
+  return hist_bin(hist_unit_value<T, MODE, UNITS, SPD>(r, un, k), un.lo, un.inv_w, nbins);
 }
 
 // one group of output channels over the fields [t0, t1) of this thread's pixels
@@ -128,7 +77,7 @@ __device__ __forceinline__ void gh_group(const GhArgs& g, const Unit (&un)[UNITS
     ra_[k].init(q);
     rb_[k].init(q + plane);
   }
-  auto consume = [&](const Raw<MA, UNITS>& a, const Raw<MB, UNITS>& b) {
+  auto consume = [&](const HistRaw<MA, UNITS>& a, const HistRaw<MB, UNITS>& b) {
 #pragma unroll
     for (int k = 0; k < UNITS; ++k) {
       if (!un[k].on) continue;                                       // wave-uniform: nothing beyond the real channels
@@ -139,21 +88,21 @@ __device__ __forceinline__ void gh_group(const GhArgs& g, const Unit (&un)[UNITS
   constexpr int U = QUAD && PAIRED ? GH_UNROLL / 2 : GH_UNROLL;
   long long t = t0;
   for (; t + U <= t1; t += U) {
-    Raw<MA, UNITS> a[U];
-    Raw<MB, UNITS> b[U];
+    HistRaw<MA, UNITS> a[U];
+    HistRaw<MB, UNITS> b[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      gh_load<TA, MA, UNITS, SPD>(g.a, t + u, i, un, a[u]);
-      if (PAIRED) gh_load<TB, MB, UNITS, SPD>(g.b, t + u, i, un, b[u]);
+      hist_unit_load<TA, MA, UNITS, SPD>(g.a, t + u, i, un, a[u]);
+      if (PAIRED) hist_unit_load<TB, MB, UNITS, SPD>(g.b, t + u, i, un, b[u]);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) consume(a[u], b[u]);
   }
   for (; t < t1; ++t) {
-    Raw<MA, UNITS> a;
-    Raw<MB, UNITS> b;
-    gh_load<TA, MA, UNITS, SPD>(g.a, t, i, un, a);
-    if (PAIRED) gh_load<TB, MB, UNITS, SPD>(g.b, t, i, un, b);
+    HistRaw<MA, UNITS> a;
+    HistRaw<MB, UNITS> b;
+    hist_unit_load<TA, MA, UNITS, SPD>(g.a, t, i, un, a);
+    if (PAIRED) hist_unit_load<TB, MB, UNITS, SPD>(g.b, t, i, un, b);
     consume(a, b);
   }
 #pragma unroll
@@ -183,12 +132,12 @@ __global__ __launch_bounds__(GH_THREADS) void gridhist_kernel(GhArgs g) {
       Unit& w = un[k];
       w.on = j < g.nout;
       w.j = w.on ? j : 0;
-      w.spd = g.speed && w.j == g.C;
+      w.spd = g.xf.speed && w.j == g.xf.C;
       any_speed |= w.spd;
-      w.c1 = w.spd ? g.su : w.j;
-      w.c2 = w.spd ? g.sv : w.j;
-      w.sc1 = g.scale[w.c1]; w.of1 = g.offset[w.c1];
-      w.sc2 = g.scale[w.c2]; w.of2 = g.offset[w.c2];
+      w.c1 = w.spd ? g.xf.su : w.j;
+      w.c2 = w.spd ? g.xf.sv : w.j;
+      w.sc1 = g.xf.scale[w.c1]; w.of1 = g.xf.offset[w.c1];
+      w.sc2 = g.xf.scale[w.c2]; w.of2 = g.xf.offset[w.c2];
       w.lo = g.lo[w.j]; w.inv_w = g.inv_w[w.j];
     }
     if (any_speed)
@@ -308,14 +257,9 @@ __global__ __launch_bounds__(GH_THREADS) void gridhist_scan_kernel(const int* co
 }
 
 bool spec_ok(const dg_hist_spec* s, int C) {
-  if (!s || s->nbins < 1 || s->nbins > DG_GRIDHIST_MAX_BINS || C < 1 || C > MAXC) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int j = 0; j < nout; ++j)
-    if (!(fabsf(s->lo[j]) <= FLT_MAX) || !(s->inv_w[j] > 0.f && s->inv_w[j] <= FLT_MAX)) return false;
-  for (int c = 0; c < C; ++c)
-    if (!(fabsf(s->scale[c]) <= FLT_MAX) || !(fabsf(s->offset[c]) <= FLT_MAX)) return false;
+  if (!s || s->nbins < 1 || s->nbins > DG_GRIDHIST_MAX_BINS || !hist_xform_ok(s, C)) return false;
+  for (int j = 0; j < hist_nout(s, C); ++j)
+    if (!hist_finite(s->lo[j]) || !(s->inv_w[j] > 0.f && s->inv_w[j] <= FLT_MAX)) return false;
   return true;
 }
 
@@ -395,14 +339,10 @@ extern "C" int dg_gridhist(const dg_eof_fields* a, const dg_eof_fields* b, const
   if ((a->dtype != DG_F32 && a->dtype != DG_BF16) || (paired && b->dtype != DG_F32 && b->dtype != DG_BF16)) return DG_ERR_BAD_DTYPE;
 
   GhArgs g;
-  g.a = GhSeries{a->base, a->ld_t, a->ld_c, a->ld_p};
-  g.b = paired ? GhSeries{b->base, b->ld_t, b->ld_c, b->ld_p} : g.a;
-  g.speed = s->speed_u >= 0 ? 1 : 0; g.su = g.speed ? s->speed_u : 0; g.sv = g.speed ? s->speed_v : 0;
-  g.C = a->C; g.P = a->P; g.T = a->T; g.nout = a->C + g.speed; g.nbins = s->nbins;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < a->C ? s->scale[c] : 1.f;
-    g.offset[c] = c < a->C ? s->offset[c] : 0.f;
-  }
+  g.a = hist_series(a);
+  g.b = paired ? hist_series(b) : g.a;
+  g.xf = hist_xform(s, a->C);
+  g.P = a->P; g.T = a->T; g.nout = hist_nout(s, a->C); g.nbins = s->nbins;
   for (int j = 0; j < MAXO; ++j) {
     g.lo[j] = j < g.nout ? s->lo[j] : 0.f;
     g.inv_w[j] = j < g.nout ? s->inv_w[j] : 1.f;
@@ -441,26 +381,15 @@ extern "C" int dg_gridhist_scan(const int32_t* counts, int nout, int S, int nbin
 
 extern "C" int dg_gridhist_host(const dg_hist_spec* s, const float* xa, const float* xb, int C, int T, int P, int32_t* counts) {
   if (!spec_ok(s, C) || T < 1 || P < 1 || !xa || !counts) return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  const int nout = C + (speed ? 1 : 0), S = xb ? 2 : 1, nb3 = s->nbins + 3;
+  const int nout = hist_nout(s, C), S = xb ? 2 : 1, nb3 = s->nbins + 3;
   for (int side = 0; side < S; ++side) {
     const float* x = side ? xb : xa;
     for (int64_t t = 0; t < T; ++t)
-      for (int64_t p = 0; p < P; ++p) {
-        float yu = 0.f, yv = 0.f;
+      for (int64_t p = 0; p < P; ++p)
         for (int j = 0; j < nout; ++j) {
-          float y;
-          if (j < C) {
-            y = hist_affine(x[(t * C + j) * P + p], s->scale[j], s->offset[j]);
-            if (j == s->speed_u) yu = y;
-            if (j == s->speed_v) yv = y;
-          } else {
-            y = hist_speed(yu, yv);
-          }
-          const int r = hist_bin(y, s->lo[j], s->inv_w[j], s->nbins);
+          const int r = hist_bin(hist_host_value(s, x + t * C * P, C, (size_t)P, (size_t)p, j), s->lo[j], s->inv_w[j], s->nbins);
           counts[(((int64_t)j * S + side) * nb3 + r) * P + p] += 1;
         }
-      }
   }
   return DG_OK;
 }

@@ -28,32 +28,26 @@ constexpr int GS_WAVES_PER_SIMD = 2;                  // the register budget: 25
 constexpr int GS_FINISH_GRID_MAX = 2048;
 constexpr int GS_BLOCKS_FULL = 1024;                  // pixel blocks of 256 that fill the chip without a T-split
 constexpr int GS_SLICE_MIN_T = 16;                    // fields per slice at least
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXK = DG_GRID_MAX_THR;
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXK = DG_GRID_MAX_THR;
 
 typedef double d4_t __attribute__((ext_vector_type(4)));
 typedef float f4_t __attribute__((ext_vector_type(4)));
 typedef int i4_t __attribute__((ext_vector_type(4)));
 
-struct GsSeries {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-};
-
 struct GsArgs {
-  GsSeries a, b;
-  int C, P, T, nout, speed, su, sv, nthr, slices, accumulate;
-  float scale[MAXC], offset[MAXC], pivot[MAXO], thr[MAXO][MAXK];
+  HistSeries a, b;
+  HistXform xf;
+  int P, T, nout, nthr, slices, accumulate;
+  float pivot[MAXO], thr[MAXO][MAXK];
   double* sums;               // the accumulators (one slice), or slice 0 of the workspace
   float* ext;
   int* cnt;
   long long slice_sums, slice_ext, slice_cnt;         // elements from one slice of the workspace to the next
 };
 
-// what one unit of state computes: output channel j from the input channels c1 (and c2: the speed)
-struct Unit {
-  int j, c1, c2;
-  bool on, spd;
-  float sc1, of1, sc2, of2, thr[MAXK];
+// what one unit of state does with its output values
+struct Unit : HistUnit {
+  float thr[MAXK];
   double pivot;
 };
 
@@ -93,58 +87,6 @@ struct Pair {
   }
 };
 
-template <int MODE, int UNITS> struct Raw { float x1[UNITS], x2[UNITS]; };
-template <int UNITS> struct Raw<HIST_PIX16, UNITS> { uint4 r; };
-
-// the loads of one field of one series for the UNITS units of this thread (i: pixel quad in HIST_NCHW4, else pixel)
-template <typename T, int MODE, int UNITS, bool SPD>
-__device__ __forceinline__ void gs_load(const GsSeries& s, long long t, long long i, const Unit (&un)[UNITS], Raw<MODE, UNITS>& r) {
-  const T* base = reinterpret_cast<const T*>(s.base);
-  if constexpr (MODE == HIST_NCHW4) {
-    const T* q = base + t * s.ld_t + 4 * i;
-    ld4(q + un[0].c1 * s.ld_c, r.x1);
-    if (SPD) ld4(q + un[0].c2 * s.ld_c, r.x2);
-  } else if constexpr (MODE == HIST_PIX16) {
-    r.r = *reinterpret_cast<const uint4*>(base + t * s.ld_t + i * s.ld_p);
-  } else {
-    const T* q = base + t * s.ld_t + i * s.ld_p;
-#pragma unroll
-    for (int k = 0; k < UNITS; ++k) {
-      r.x1[k] = ld_elem(q + un[k].c1 * s.ld_c);
-      r.x2[k] = r.x1[k];
-      if (un[k].spd) r.x2[k] = ld_elem(q + un[k].c2 * s.ld_c);       // wave-uniform
-    }
-  }
-}
-
-// channel c (wave-uniform) of the 16 bytes of one pixel: shifts of the two 64-bit halves, no register array to index
-template <typename T>
-__device__ __forceinline__ float gs_pick(const uint4& r, int c) {
-  const unsigned long long lo = ((unsigned long long)r.y << 32) | r.x, hi = ((unsigned long long)r.w << 32) | r.z;
-  if (sizeof(T) == 2) {
-    const unsigned long long q = c < 4 ? lo : hi;
-    return __uint_as_float((unsigned)(q >> (16 * (c & 3))) << 16);
-  }
-  const unsigned long long q = c < 2 ? lo : hi;                      // fp32: C <= 4 in this mode
-  return __uint_as_float((unsigned)(q >> (32 * (c & 1))));
-}
-
-// the output value of unit k
-template <typename T, int MODE, int UNITS, bool SPD>
-__device__ __forceinline__ float gs_value(const Raw<MODE, UNITS>& r, const Unit& un, int k) {
-  float x1, x2;
-  if constexpr (MODE == HIST_PIX16) {
-    x1 = gs_pick<T>(r.r, un.c1);
-    x2 = SPD ? gs_pick<T>(r.r, un.c2) : x1;
-  } else {
-    x1 = r.x1[k];
-    x2 = MODE == HIST_NCHW4 && !SPD ? x1 : r.x2[k];
-  }
-  float y = hist_affine(x1, un.sc1, un.of1);
-  if (SPD && un.spd) y = hist_speed(y, hist_affine(x2, un.sc2, un.of2));   // wave-uniform
-  return y;
-}
-
 __device__ __forceinline__ void put(double* q, double v, bool acc) { *q = acc ? *q + v : v; }
 __device__ __forceinline__ void put(int* q, int v, bool acc) { *q = acc ? *q + v : v; }
 __device__ __forceinline__ void put_min(float* q, float v, bool acc) { *q = acc ? fminf(*q, v) : v; }
@@ -180,14 +122,14 @@ __device__ __forceinline__ void gs_group(const GsArgs& g, const Unit (&un)[UNITS
 #pragma unroll
   for (int k = 0; k < UNITS; ++k) { sa[k].init(); sb[k].init(); pr[k].init(); }
 
-  auto consume = [&](const Raw<MA, UNITS>& ra, const Raw<MB, UNITS>& rb) {
+  auto consume = [&](const HistRaw<MA, UNITS>& ra, const HistRaw<MB, UNITS>& rb) {
 #pragma unroll
     for (int k = 0; k < UNITS; ++k) {
-      const float ya = gs_value<TA, MA, UNITS, SPD>(ra, un[k], k);
+      const float ya = hist_unit_value<TA, MA, UNITS, SPD>(ra, un[k], k);
       const bool fa = fabsf(ya) <= FLT_MAX;                          // false for NaN and +-inf
       const double ua = sa[k].add(ya, fa, un[k]);
       if (PAIRED) {
-        const float yb = gs_value<TB, MB, UNITS, SPD>(rb, un[k], k);
+        const float yb = hist_unit_value<TB, MB, UNITS, SPD>(rb, un[k], k);
         const bool fb = fabsf(yb) <= FLT_MAX;
         const double ub = sb[k].add(yb, fb, un[k]);
         pr[k].add(ya, yb, fa, fb, ua, ub);
@@ -197,21 +139,21 @@ __device__ __forceinline__ void gs_group(const GsArgs& g, const Unit (&un)[UNITS
   constexpr int U = QUAD && PAIRED ? GS_UNROLL / 2 : GS_UNROLL;
   long long t = t0;
   for (; t + U <= t1; t += U) {
-    Raw<MA, UNITS> ra[U];
-    Raw<MB, UNITS> rb[U];
+    HistRaw<MA, UNITS> ra[U];
+    HistRaw<MB, UNITS> rb[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      gs_load<TA, MA, UNITS, SPD>(g.a, t + u, i, un, ra[u]);
-      if (PAIRED) gs_load<TB, MB, UNITS, SPD>(g.b, t + u, i, un, rb[u]);
+      hist_unit_load<TA, MA, UNITS, SPD>(g.a, t + u, i, un, ra[u]);
+      if (PAIRED) hist_unit_load<TB, MB, UNITS, SPD>(g.b, t + u, i, un, rb[u]);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) consume(ra[u], rb[u]);
   }
   for (; t < t1; ++t) {
-    Raw<MA, UNITS> ra;
-    Raw<MB, UNITS> rb;
-    gs_load<TA, MA, UNITS, SPD>(g.a, t, i, un, ra);
-    if (PAIRED) gs_load<TB, MB, UNITS, SPD>(g.b, t, i, un, rb);
+    HistRaw<MA, UNITS> ra;
+    HistRaw<MB, UNITS> rb;
+    hist_unit_load<TA, MA, UNITS, SPD>(g.a, t, i, un, ra);
+    if (PAIRED) hist_unit_load<TB, MB, UNITS, SPD>(g.b, t, i, un, rb);
     consume(ra, rb);
   }
 
@@ -302,12 +244,12 @@ __global__ __launch_bounds__(GS_THREADS, GS_WAVES_PER_SIMD) void gridstats_kerne
       Unit& w = un[k];
       w.on = j < g.nout;
       w.j = w.on ? j : 0;
-      w.spd = g.speed && w.j == g.C;
+      w.spd = g.xf.speed && w.j == g.xf.C;
       any_speed |= w.spd;
-      w.c1 = w.spd ? g.su : w.j;
-      w.c2 = w.spd ? g.sv : w.j;
-      w.sc1 = g.scale[w.c1]; w.of1 = g.offset[w.c1];
-      w.sc2 = g.scale[w.c2]; w.of2 = g.offset[w.c2];
+      w.c1 = w.spd ? g.xf.su : w.j;
+      w.c2 = w.spd ? g.xf.sv : w.j;
+      w.sc1 = g.xf.scale[w.c1]; w.of1 = g.xf.offset[w.c1];
+      w.sc2 = g.xf.scale[w.c2]; w.of2 = g.xf.offset[w.c2];
       w.pivot = (double)g.pivot[w.j];
 #pragma unroll
       for (int q = 0; q < MAXK; ++q) w.thr[q] = q < g.nthr ? g.thr[w.j][q] : INFINITY;
@@ -342,21 +284,12 @@ __global__ __launch_bounds__(GS_THREADS) void gridstats_finish_kernel(const doub
   }
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 bool spec_ok(const dg_grid_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC || s->nthr < 0 || s->nthr > MAXK) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
-  for (int j = 0; j < nout; ++j) {
-    if (!finite_f(s->pivot[j])) return false;
-    for (int k = 0; k < s->nthr; ++k)
-      if (!finite_f(s->thr[j][k])) return false;
-  }
-  return true;
+  if (!s || s->nthr < 0 || s->nthr > MAXK || !hist_xform_ok(s, C)) return false;
+  const int nout = hist_nout(s, C);
+  for (int j = 0; j < nout; ++j)
+    if (!hist_finite(s->pivot[j])) return false;
+  return hist_thr_ok(s->thr, nout, s->nthr);
 }
 
 int slices_of(int T, int P) {
@@ -368,8 +301,6 @@ int slices_of(int T, int P) {
   return s < 1 ? 1 : s;
 }
 
-size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
 struct Layout {
   int nout, NS, NE, NC, S;
   size_t n_s, n_e, n_c;       // elements of one slice = of the accumulators
@@ -378,7 +309,7 @@ struct Layout {
 
 Layout layout_of(const dg_eof_fields* a, bool paired, const dg_grid_spec* s) {
   Layout l;
-  l.nout = a->C + (s->speed_u >= 0 ? 1 : 0);
+  l.nout = hist_nout(s, a->C);
   l.NS = paired ? 12 : 4;
   l.NE = paired ? 4 : 2;
   l.NC = paired ? 3 + 2 * s->nthr : 1 + s->nthr;
@@ -389,9 +320,9 @@ Layout layout_of(const dg_eof_fields* a, bool paired, const dg_grid_spec* s) {
     l.off_e = l.off_c = 0;
     l.bytes = 256;
   } else {
-    l.off_e = round256(l.S * l.n_s * sizeof(double));
-    l.off_c = l.off_e + round256(l.S * l.n_e * sizeof(float));
-    l.bytes = l.off_c + round256(l.S * l.n_c * sizeof(int));
+    l.off_e = hist_round256(l.S * l.n_s * sizeof(double));
+    l.off_c = l.off_e + hist_round256(l.S * l.n_e * sizeof(float));
+    l.bytes = l.off_c + hist_round256(l.S * l.n_c * sizeof(int));
   }
   return l;
 }
@@ -460,19 +391,13 @@ extern "C" int dg_gridstats(const dg_eof_fields* a, const dg_eof_fields* b, cons
   if ((a->dtype != DG_F32 && a->dtype != DG_BF16) || (paired && b->dtype != DG_F32 && b->dtype != DG_BF16)) return DG_ERR_BAD_DTYPE;
 
   GsArgs g;
-  g.a = GsSeries{a->base, a->ld_t, a->ld_c, a->ld_p};
-  g.b = paired ? GsSeries{b->base, b->ld_t, b->ld_c, b->ld_p} : g.a;
-  g.C = a->C; g.P = a->P; g.T = a->T; g.nout = l.nout;
-  g.speed = s->speed_u >= 0 ? 1 : 0; g.su = g.speed ? s->speed_u : 0; g.sv = g.speed ? s->speed_v : 0;
+  g.a = hist_series(a);
+  g.b = paired ? hist_series(b) : g.a;
+  g.xf = hist_xform(s, a->C);
+  g.P = a->P; g.T = a->T; g.nout = l.nout;
   g.nthr = s->nthr; g.slices = l.S; g.accumulate = l.S == 1 ? 1 : 0;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < a->C ? s->scale[c] : 1.f;
-    g.offset[c] = c < a->C ? s->offset[c] : 0.f;
-  }
-  for (int j = 0; j < MAXO; ++j) {
-    g.pivot[j] = j < l.nout ? s->pivot[j] : 0.f;
-    for (int k = 0; k < MAXK; ++k) g.thr[j][k] = j < l.nout && k < s->nthr ? s->thr[j][k] : INFINITY;
-  }
+  for (int j = 0; j < MAXO; ++j) g.pivot[j] = j < l.nout ? s->pivot[j] : 0.f;
+  hist_thr_pad(s->thr, l.nout, s->nthr, g.thr);
   char* w = reinterpret_cast<char*>(ws);
   if (l.S == 1) {
     g.sums = sums; g.ext = extrema; g.cnt = counts;

@@ -24,52 +24,16 @@ constexpr long long HIST_ITEMS_MAX = 1LL << 20;       // items per thread per la
 constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT;
 
 struct HistArgs {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-  int C, P, nbins, speed, su, sv;
+  HistSeries x;
+  HistXform xf;
+  int P, nbins;
   long long t0, items;        // fields t0 .. of this launch; items = fields * items per field
   int ipf;                    // items per field
-  float lo[MAXO], inv_w[MAXO], scale[MAXC], offset[MAXC];
+  float lo[MAXO], inv_w[MAXO];
   unsigned long long* counts; // int64 [nout][nbins + 3]
   double* part_m;             // [grid][MAXO][2]
   float* part_e;              // [grid][MAXO][2]
 };
-
-__device__ __forceinline__ double shfl_xor_d(double v, int m) {
-  return __longlong_as_double(__shfl_xor(__double_as_longlong(v), m, 64));
-}
-
-template <typename T, int MODE>
-__device__ __forceinline__ void load_item(const HistArgs& a, long long t, long long i, float (&v)[4][MAXC]) {
-  const T* base = reinterpret_cast<const T*>(a.base);
-  if (MODE == HIST_NCHW4) {
-    const T* q = base + t * a.ld_t + 4 * i;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      if (c < a.C) {
-        float w[4];
-        ld4(q + c * a.ld_c, w);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k][c] = w[k];
-      }
-    }
-  } else if (MODE == HIST_PIX16) {
-    const uint4 r = *reinterpret_cast<const uint4*>(base + t * a.ld_t + i * a.ld_p);
-    const unsigned u[4] = {r.x, r.y, r.z, r.w};
-    if (sizeof(T) == 2) {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[0][c] = __uint_as_float(c & 1 ? u[c / 2] & 0xffff0000u : u[c / 2] << 16);
-    } else {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[0][c] = c < 4 ? __uint_as_float(u[c & 3]) : 0.f;
-    }
-  } else {
-    const T* q = base + t * a.ld_t + i * a.ld_p;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-      if (c < a.C) v[0][c] = ld_elem(q + c * a.ld_c);
-  }
-}
 
 struct Acc {
   double s1, s2;
@@ -90,7 +54,8 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_kernel(HistArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned int hist_lds[];    // [nout][nbins + 3]
   __shared__ double red_m[HIST_THREADS / 64][MAXO][2];
   __shared__ float red_e[HIST_THREADS / 64][MAXO][2];
-  const int nb3 = a.nbins + 3, nout = a.C + a.speed;
+  const HistXform& xf = a.xf;
+  const int nb3 = a.nbins + 3, nout = xf.C + xf.speed;
   for (int i = threadIdx.x; i < nout * nb3; i += HIST_THREADS) hist_lds[i] = 0u;
   __syncthreads();
   Acc acc[MAXO];
@@ -103,7 +68,7 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_kernel(HistArgs a) {
   long long t = a.t0 + g0 / a.ipf, i = g0 % a.ipf;
   for (long long g = g0; g < a.items; g += stride) {
     float v[4][MAXC];
-    load_item<T, MODE>(a, t, i, v);
+    hist_load_item<T, MODE>(a.x, xf.C, t, i, v);
     t += dt;
     i += di;
     if (i >= a.ipf) { i -= a.ipf; ++t; }
@@ -112,17 +77,17 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_kernel(HistArgs a) {
       float yu = 0.f, yv = 0.f;
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) {
-        if (c < a.C) {
-          const float y = hist_affine(v[k][c], a.scale[c], a.offset[c]);
+        if (c < xf.C) {
+          const float y = hist_affine(v[k][c], xf.scale[c], xf.offset[c]);
           atomicAdd(&hist_lds[c * nb3 + hist_bin(y, a.lo[c], a.inv_w[c], a.nbins)], 1u);
           acc[c].add(y);
-          yu = c == a.su ? y : yu;
-          yv = c == a.sv ? y : yv;
+          yu = c == xf.su ? y : yu;
+          yv = c == xf.sv ? y : yv;
         }
       }
-      if (a.speed) {
+      if (xf.speed) {
         const float s = hist_speed(yu, yv);
-        atomicAdd(&hist_lds[a.C * nb3 + hist_bin(s, a.lo[a.C], a.inv_w[a.C], a.nbins)], 1u);
+        atomicAdd(&hist_lds[xf.C * nb3 + hist_bin(s, a.lo[xf.C], a.inv_w[xf.C], a.nbins)], 1u);
         acc[MAXO - 1].add(s);
       }
     }
@@ -137,8 +102,8 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_kernel(HistArgs a) {
 #pragma unroll
   for (int j = 0; j < MAXO; ++j) {
     for (int m = 32; m >= 1; m >>= 1) {
-      acc[j].s1 += shfl_xor_d(acc[j].s1, m);
-      acc[j].s2 += shfl_xor_d(acc[j].s2, m);
+      acc[j].s1 += hist_shfl_xor_f64(acc[j].s1, m);
+      acc[j].s2 += hist_shfl_xor_f64(acc[j].s2, m);
       acc[j].mn = fminf(acc[j].mn, __shfl_xor(acc[j].mn, m, 64));
       acc[j].mx = fmaxf(acc[j].mx, __shfl_xor(acc[j].mx, m, 64));
     }
@@ -197,14 +162,9 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_finish_kernel(const double*
 }
 
 bool spec_ok(const dg_hist_spec* s, int C) {
-  if (!s || s->nbins < 1 || s->nbins > DG_HIST_MAX_BINS || C < 1 || C > MAXC) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int j = 0; j < nout; ++j)
-    if (!(fabsf(s->lo[j]) <= FLT_MAX) || !(s->inv_w[j] > 0.f && s->inv_w[j] <= FLT_MAX)) return false;
-  for (int c = 0; c < C; ++c)
-    if (!(fabsf(s->scale[c]) <= FLT_MAX) || !(fabsf(s->offset[c]) <= FLT_MAX)) return false;
+  if (!s || s->nbins < 1 || s->nbins > DG_HIST_MAX_BINS || !hist_xform_ok(s, C)) return false;
+  for (int j = 0; j < hist_nout(s, C); ++j)
+    if (!hist_finite(s->lo[j]) || !(s->inv_w[j] > 0.f && s->inv_w[j] <= FLT_MAX)) return false;
   return true;
 }
 
@@ -229,17 +189,10 @@ extern "C" size_t dg_hist_ws_bytes(const dg_eof_fields* x, const dg_hist_spec* s
 
 extern "C" int dg_hist_host_bins(const dg_hist_spec* s, const float* x, int C, int64_t n, int32_t* bins) {
   if (!spec_ok(s, C) || n < 0 || (n > 0 && (!x || !bins))) return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  for (int64_t i = 0; i < n; ++i) {
-    float yu = 0.f, yv = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float y = hist_affine(x[(int64_t)c * n + i], s->scale[c], s->offset[c]);
-      bins[(int64_t)c * n + i] = hist_bin(y, s->lo[c], s->inv_w[c], s->nbins);
-      if (c == s->speed_u) yu = y;
-      if (c == s->speed_v) yv = y;
-    }
-    if (speed) bins[(int64_t)C * n + i] = hist_bin(hist_speed(yu, yv), s->lo[C], s->inv_w[C], s->nbins);
-  }
+  const int nout = hist_nout(s, C);
+  for (int64_t i = 0; i < n; ++i)
+    for (int j = 0; j < nout; ++j)
+      bins[(int64_t)j * n + i] = hist_bin(hist_host_value(s, x, C, (size_t)n, (size_t)i, j), s->lo[j], s->inv_w[j], s->nbins);
   return DG_OK;
 }
 
@@ -248,18 +201,15 @@ extern "C" int dg_hist(const dg_eof_fields* x, const dg_hist_spec* s, void* ws, 
   if (!hist_fields_ok(x) || !spec_ok(s, x->C) || !ws || !counts || !moments || !extrema) return DG_ERR_BAD_SHAPE;
   if (x->dtype != DG_F32 && x->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
   const int mode = hist_mode(x);
-  const int speed = s->speed_u >= 0 ? 1 : 0, nout = x->C + speed;
+  const int nout = hist_nout(s, x->C);
   HistArgs a;
-  a.base = x->base; a.ld_t = x->ld_t; a.ld_c = x->ld_c; a.ld_p = x->ld_p;
-  a.C = x->C; a.P = x->P; a.nbins = s->nbins; a.speed = speed; a.su = s->speed_u; a.sv = s->speed_v;
+  a.x = hist_series(x);
+  a.xf = hist_xform(s, x->C);
+  a.P = x->P; a.nbins = s->nbins;
   a.ipf = mode == HIST_NCHW4 ? x->P / 4 : x->P;
   for (int j = 0; j < MAXO; ++j) {
     a.lo[j] = j < nout ? s->lo[j] : 0.f;
     a.inv_w[j] = j < nout ? s->inv_w[j] : 1.f;
-  }
-  for (int c = 0; c < MAXC; ++c) {
-    a.scale[c] = c < x->C ? s->scale[c] : 1.f;
-    a.offset[c] = c < x->C ? s->offset[c] : 0.f;
   }
   a.counts = reinterpret_cast<unsigned long long*>(counts);
   a.part_m = reinterpret_cast<double*>(ws);
@@ -273,13 +223,8 @@ extern "C" int dg_hist(const dg_eof_fields* x, const dg_hist_spec* s, void* ws, 
     a.t0 = t0;
     a.items = nt * a.ipf;
     const int grid = hist_grid(a.items);
-    int rc;
-    if (x->dtype == DG_F32)
-      rc = mode == HIST_NCHW4 ? launch<float, HIST_NCHW4>(a, grid, lds, st)
-         : mode == HIST_PIX16 ? launch<float, HIST_PIX16>(a, grid, lds, st) : launch<float, HIST_ANY>(a, grid, lds, st);
-    else
-      rc = mode == HIST_NCHW4 ? launch<bf16_t, HIST_NCHW4>(a, grid, lds, st)
-         : mode == HIST_PIX16 ? launch<bf16_t, HIST_PIX16>(a, grid, lds, st) : launch<bf16_t, HIST_ANY>(a, grid, lds, st);
+    // t, m: tags of the element type and the load mode (hist_common.h "dtype x load mode"): decltype(m)::value is the HIST_* constant
+    const int rc = hist_dispatch(x->dtype, mode, [&](auto t, auto m) { return launch<decltype(t), decltype(m)::value>(a, grid, lds, st); });
     if (rc != DG_OK) return rc;
     hipLaunchKernelGGL(hist_finish_kernel, dim3(nout), dim3(HIST_THREADS), 0, st, (const double*)a.part_m, (const float*)a.part_e,
                        grid, x->C, moments, extrema);

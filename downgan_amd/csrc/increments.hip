@@ -38,7 +38,7 @@ constexpr int INCR_TABLE_CELLS = 12288;                 // uint32 cells of a gro
 constexpr int INCR_TILE_FLOATS = 24576;                 // the staged tile of one output channel: 96 KiB
 constexpr int INCR_AW0 = 512, INCR_AW1 = 64;            // anchor columns of a tile, direction 0 / 1
 constexpr long long INCR_WG_TILES_MAX = 131072;         // tiles per workgroup per launch: (2^17 + 1) * 24576 < 2^32, no wrap
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXL = DG_INCR_MAX_LAGS;
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXL = DG_INCR_MAX_LAGS;
 static_assert((SUB & (SUB - 1)) == 0 && SUB >= 1 && SUB <= INCR_WAVES, "sub-tables");
 static_assert(MAXL * (DG_INCR_MAX_BINS + 4) <= INCR_TABLE_CELLS, "one output channel must fit the table budget");
 static_assert((INCR_TABLE_CELLS + INCR_TILE_FLOATS) * 4 + 8192 <= 160 * 1024, "LDS budget");
@@ -46,24 +46,19 @@ static_assert(INCR_TILE_FLOATS / ((INCR_AW0 + DG_INCR_MAX_LAG + 3) / 4 * 4) >= 1
 static_assert((INCR_WG_TILES_MAX + 1) * INCR_TILE_FLOATS < (1LL << 32), "no uint32 wrap");
 
 struct IncrArgs {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-  int C, H, W, su, sv;
+  HistSeries x;
+  int C, H, W, su, sv;                                  // C, su, sv, scale, offset: HistXform's members, not embedded (run_series)
   int nlag, nbins, dir, sub;                            // sub: copies of the tables (SUB, fewer when they would not fit)
   int R, CW, AH, AW, tiles_h, tiles_w;                  // tile rows / columns staged, anchor rows / columns, tiles per field
   long long t0, ntiles;                                 // fields t0 .. of this launch; ntiles = fields * tiles per field
   int jn, chan[MAXO];                                   // the output channels of this group
   int lag[MAXL];
-  float scale[MAXC], offset[MAXC];
+  float scale[HIST_MAXC], offset[HIST_MAXC];
   float lo[MAXO][MAXL], inv_w[MAXO][MAXL];              // [channel of the group][lag]
   unsigned long long* counts;                           // the series' [nout][2][nlag][nbins + 3]
   unsigned long long* finite;                           // the series' [nout][2][nlag]
   double* part;                                         // [grid][MAXO][MAXL][6]
 };
-
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-  return __longlong_as_double(__shfl_xor(__double_as_longlong(v), m, 64));
-}
 
 // the six terms of one increment (shared with the host reference)
 struct IncrTerms { double v[6]; };
@@ -72,24 +67,14 @@ __host__ __device__ inline IncrTerms incr_terms(float d) {
   const double u = (double)d, u2 = u * u, u3 = u2 * u, u4 = u2 * u2;
   return IncrTerms{{u, __builtin_fabs(u), u2, u3, __builtin_fabs(u3), u4}};
 }
-__host__ __device__ inline bool incr_finite(float d) { return __builtin_fabsf(d) <= FLT_MAX; }   // false for NaN and +-inf
 
 // output channel j of pixel p of one field, element by element
 template <typename T>
 __device__ __forceinline__ float incr_value(const IncrArgs& a, const T* f, int j, long long p) {
-  const T* q = f + p * a.ld_p;
-  if (j < a.C) return hist_affine(ld_elem(q + j * a.ld_c), a.scale[j], a.offset[j]);
-  return hist_speed(hist_affine(ld_elem(q + a.su * a.ld_c), a.scale[a.su], a.offset[a.su]),
-                    hist_affine(ld_elem(q + a.sv * a.ld_c), a.scale[a.sv], a.offset[a.sv]));
-}
-
-// channel c of a pixel loaded as 16 bytes (HIST_PIX16)
-template <typename T>
-__device__ __forceinline__ float pix16_channel(const uint4& r, int c) {
-  const int w = sizeof(T) == 2 ? c >> 1 : c;
-  const unsigned word = w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w;
-  if (sizeof(T) == 2) return __uint_as_float(c & 1 ? word & 0xffff0000u : word << 16);
-  return __uint_as_float(word);
+  const T* q = f + p * a.x.ld_p;
+  if (j < a.C) return hist_affine(ld_elem(q + j * a.x.ld_c), a.scale[j], a.offset[j]);
+  return hist_speed(hist_affine(ld_elem(q + a.su * a.x.ld_c), a.scale[a.su], a.offset[a.su]),
+                    hist_affine(ld_elem(q + a.sv * a.x.ld_c), a.scale[a.sv], a.offset[a.sv]));
 }
 
 template <typename T, int MODE>
@@ -116,7 +101,7 @@ __global__ __launch_bounds__(INCR_THREADS) void incr_kernel(IncrArgs a) {
     const int h0 = th * a.AH, w0 = tw * a.AW;
     const int re = min(a.R, a.H - h0), ce = min(a.CW, a.W - w0);         // rows / columns staged
     const int ah = min(a.AH, a.H - h0), aw = min(a.AW, a.W - w0);        // anchor rows / columns
-    const T* f = reinterpret_cast<const T*>(a.base) + t * a.ld_t;
+    const T* f = reinterpret_cast<const T*>(a.x.base) + t * a.x.ld_t;
     for (int jj = 0; jj < a.jn; ++jj) {
       const int j = a.chan[jj];
 #ifndef DG_INCR_NAIVE
@@ -129,8 +114,8 @@ __global__ __launch_bounds__(INCR_THREADS) void incr_kernel(IncrArgs a) {
           const int r = i / c4n, q = i - r * c4n;
           const T* p = f + (long long)(h0 + r) * a.W + w0 + 4 * q;
           float v0[4], v1[4];
-          ld4(p + c0 * a.ld_c, v0);
-          if (spd) ld4(p + c1 * a.ld_c, v1);
+          ld4(p + c0 * a.x.ld_c, v0);
+          if (spd) ld4(p + c1 * a.x.ld_c, v1);
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const float y = hist_affine(v0[k], sc0, of0);
@@ -140,9 +125,9 @@ __global__ __launch_bounds__(INCR_THREADS) void incr_kernel(IncrArgs a) {
       } else if (MODE == HIST_PIX16) {
         for (int i = tid; i < re * ce; i += INCR_THREADS) {
           const int r = i / ce, c = i - r * ce;
-          const uint4 px = *reinterpret_cast<const uint4*>(f + ((long long)(h0 + r) * a.W + w0 + c) * a.ld_p);
-          const float y = hist_affine(pix16_channel<T>(px, c0), sc0, of0);
-          tile[r * a.CW + c] = spd ? hist_speed(y, hist_affine(pix16_channel<T>(px, c1), sc1, of1)) : y;
+          const uint4 px = *reinterpret_cast<const uint4*>(f + ((long long)(h0 + r) * a.W + w0 + c) * a.x.ld_p);
+          const float y = hist_affine(hist_pick16_sel<T>(px, c0), sc0, of0);
+          tile[r * a.CW + c] = spd ? hist_speed(y, hist_affine(hist_pick16_sel<T>(px, c1), sc1, of1)) : y;
         }
       } else {
         for (int i = tid; i < re * ce; i += INCR_THREADS) {
@@ -179,7 +164,7 @@ __global__ __launch_bounds__(INCR_THREADS) void incr_kernel(IncrArgs a) {
             const float d = hist_diff(incr_value<T>(a, f, j, p0 + (a.dir ? (long long)a.lag[l] * a.W : a.lag[l])), y0);
 #endif
             atomicAdd(&tab[(jj * a.nlag + l) * nb4 + hist_bin(d, a.lo[jj][l], a.inv_w[jj][l], a.nbins)], 1u);
-            const bool fin = incr_finite(d);
+            const bool fin = hist_finite(d);
             const IncrTerms e = incr_terms(fin ? d : 0.f);
             nf[l] += fin ? 1u : 0u;
 #pragma unroll
@@ -194,7 +179,7 @@ __global__ __launch_bounds__(INCR_THREADS) void incr_kernel(IncrArgs a) {
           for (int s = 32; s >= 1; s >>= 1) {
             nf[l] += __shfl_xor(nf[l], s, 64);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) m[l][k] += shfl_xor_f64(m[l][k], s);
+            for (int k = 0; k < 6; ++k) m[l][k] += hist_shfl_xor_f64(m[l][k], s);
           }
           if (lane == 0) {
             if (nf[l]) atomicAdd(&tab[(jj * a.nlag + l) * nb4 + a.nbins + 3], nf[l]);
@@ -251,20 +236,13 @@ __global__ __launch_bounds__(256) void incr_finish_kernel(const double* part, in
   if (threadIdx.x < 6) moments[(((long long)a.chan[jj] * 2 + a.dir) * a.nlag + l) * 6 + threadIdx.x] += sm[0][threadIdx.x];
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 bool spec_ok(const dg_incr_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC || s->nlag < 1 || s->nlag > MAXL || s->nbins < 1 || s->nbins > DG_INCR_MAX_BINS) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
+  if (!s || s->nlag < 1 || s->nlag > MAXL || s->nbins < 1 || s->nbins > DG_INCR_MAX_BINS || !hist_xform_ok(s, C)) return false;
   for (int l = 0; l < s->nlag; ++l)
     if (s->lag[l] < 1 || s->lag[l] > DG_INCR_MAX_LAG || (l > 0 && s->lag[l] <= s->lag[l - 1])) return false;
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int j = 0; j < nout; ++j)
+  for (int j = 0; j < hist_nout(s, C); ++j)
     for (int l = 0; l < s->nlag; ++l)
-      if (!finite_f(s->lo[j][l]) || !(s->inv_w[j][l] > 0.f && s->inv_w[j][l] <= FLT_MAX)) return false;
+      if (!hist_finite(s->lo[j][l]) || !(s->inv_w[j][l] > 0.f && s->inv_w[j][l] <= FLT_MAX)) return false;
   return true;
 }
 
@@ -284,29 +262,23 @@ int launch(const IncrArgs& a, int grid, size_t lds, hipStream_t st) {
   return DG_OK;
 }
 
-template <typename T>
-int launch_mode(int mode, const IncrArgs& a, int grid, size_t lds, hipStream_t st) {
-  return mode == HIST_NCHW4 ? launch<T, HIST_NCHW4>(a, grid, lds, st)
-       : mode == HIST_PIX16 ? launch<T, HIST_PIX16>(a, grid, lds, st) : launch<T, HIST_ANY>(a, grid, lds, st);
-}
-
 constexpr size_t INCR_WS_BYTES = (size_t)INCR_CUS * MAXO * MAXL * 6 * sizeof(double);
 
 // one series: both directions, every group of output channels
 int run_series(const dg_eof_fields* x, int H, int W, const dg_incr_spec* s, void* ws, int64_t* counts, int64_t* finite,
                double* moments, hipStream_t st) {
-  const int C = x->C, nout = C + (s->speed_u >= 0 ? 1 : 0), nb4 = s->nbins + 4;
+  const int C = x->C, nout = hist_nout(s, C), nb4 = s->nbins + 4;
   int mode = hist_mode(x);
   if (mode == HIST_NCHW4 && W % 4 != 0) mode = HIST_ANY;                 // rows of such a W are not 16-byte aligned
   IncrArgs g;
-  g.base = x->base; g.ld_t = x->ld_t; g.ld_c = x->ld_c; g.ld_p = x->ld_p;
-  g.C = C; g.H = H; g.W = W;
-  g.su = s->speed_u >= 0 ? s->speed_u : 0; g.sv = s->speed_u >= 0 ? s->speed_v : 0;
+  g.x = hist_series(x);
+  // incr_kernel runs at 106 SGPRs and reads its arguments again inside its loops.  With a HistXform embedded in front of H / W
+  // it took 0.5 - 0.7 % longer on Gaussian fields at the same registers (profiles/field_reader_refactor.json), so the argument
+  // layout stays as it was measured and the padded transform is copied in member by member.
+  const HistXform xf = hist_xform(s, C);
+  g.C = xf.C; g.H = H; g.W = W; g.su = xf.su; g.sv = xf.sv;
+  for (int c = 0; c < HIST_MAXC; ++c) { g.scale[c] = xf.scale[c]; g.offset[c] = xf.offset[c]; }
   g.nbins = s->nbins;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < C ? s->scale[c] : 1.f;
-    g.offset[c] = c < C ? s->offset[c] : 0.f;
-  }
   g.counts = reinterpret_cast<unsigned long long*>(counts);
   g.finite = reinterpret_cast<unsigned long long*>(finite);
   g.part = reinterpret_cast<double*>(ws);
@@ -358,7 +330,7 @@ int run_series(const dg_eof_fields* x, int H, int W, const dg_incr_spec* s, void
         g.t0 = t0;
         g.ntiles = nt * tpf;
         const int grid = (int)(g.ntiles < INCR_CUS ? g.ntiles : INCR_CUS);
-        const int rc = x->dtype == DG_F32 ? launch_mode<float>(mode, g, grid, lds, st) : launch_mode<bf16_t>(mode, g, grid, lds, st);
+        const int rc = hist_dispatch(x->dtype, mode, [&](auto t, auto m) { return launch<decltype(t), decltype(m)::value>(g, grid, lds, st); });
         if (rc != DG_OK) return rc;
         hipLaunchKernelGGL(incr_finish_kernel, dim3(g.jn * g.nlag), dim3(256), 0, st, (const double*)g.part, grid, g, moments);
       }
@@ -376,14 +348,11 @@ extern "C" size_t dg_incr_ws_bytes(const dg_eof_fields* a, const dg_eof_fields* 
 extern "C" int dg_incr_host(const dg_incr_spec* s, const float* x, int C, int H, int W, int64_t* counts, int64_t* finite,
                             double* moments) {
   if (!spec_ok(s, C) || !grid_ok(H, W) || !x || !counts || !finite || !moments) return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  const int nout = C + (speed ? 1 : 0), nb3 = s->nbins + 3;
+  const int nout = hist_nout(s, C), nb3 = s->nbins + 3;
   const size_t P = (size_t)H * W;
   std::vector<float> y((size_t)nout * P);
-  for (int c = 0; c < C; ++c)
-    for (size_t p = 0; p < P; ++p) y[c * P + p] = hist_affine(x[c * P + p], s->scale[c], s->offset[c]);
-  if (speed)
-    for (size_t p = 0; p < P; ++p) y[C * P + p] = hist_speed(y[s->speed_u * P + p], y[s->speed_v * P + p]);
+  for (int j = 0; j < nout; ++j)
+    for (size_t p = 0; p < P; ++p) y[j * P + p] = hist_host_value(s, x, C, P, p, j);
   for (int j = 0; j < nout; ++j) {
     const float* yj = y.data() + j * P;
     for (int dir = 0; dir < 2; ++dir) {
@@ -397,7 +366,7 @@ extern "C" int dg_incr_host(const dg_incr_spec* s, const float* x, int C, int H,
             const size_t p = (size_t)h * W + w;
             const float d = hist_diff(yj[p + step], yj[p]);
             counts[row * nb3 + hist_bin(d, s->lo[j][l], s->inv_w[j][l], s->nbins)] += 1;
-            if (incr_finite(d)) {
+            if (hist_finite(d)) {
               const IncrTerms e = incr_terms(d);
               finite[row] += 1;
               for (int k = 0; k < 6; ++k) moments[row * 6 + k] += e.v[k];
@@ -415,7 +384,7 @@ extern "C" int dg_incr(const dg_eof_fields* a, const dg_eof_fields* b, int H, in
   if (!call_ok(a, b, H, W, s) || !ws || !counts || !finite || !moments) return DG_ERR_BAD_SHAPE;
   if (!dtype_ok(a) || (b && !dtype_ok(b))) return DG_ERR_BAD_DTYPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long nout = a->C + (s->speed_u >= 0 ? 1 : 0), rows = nout * 2 * s->nlag;
+  const long long nout = hist_nout(s, a->C), rows = nout * 2 * s->nlag;
   for (int ser = 0; ser < (b ? 2 : 1); ++ser) {
     const int rc = run_series(ser ? b : a, H, W, s, ws, counts + ser * rows * (s->nbins + 3), finite + ser * rows,
                               moments + ser * rows * 6, st);

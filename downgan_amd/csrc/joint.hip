@@ -26,59 +26,23 @@ constexpr long long JOINT_WG_ITEMS_MAX = 1LL << 28;     // items per workgroup p
 constexpr int MAXC = DG_EOF_MAX_C, MAXP = DG_HIST2D_MAX_PAIRS, MAXK = DG_HIST2D_MAX_SECTORS / 4;
 static_assert(JOINT_LDS_CELLS >= DG_HIST2D_MAX_CELLS && JOINT_LDS_CELLS * 4 <= 160 * 1024 - 1024, "LDS budget");
 
-struct JointSeries {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-};
-
 struct JointAxis {
   int src, chan, nbins;
   float lo, inv_w;
 };
 
 struct JointArgs {
-  JointSeries s[2];
-  int C, npairs, cells, su, sv, K;                      // pairs and cells of this group
+  HistSeries s[2];
+  int npairs, cells, K;                                 // pairs and cells of this group
   int use[2], need_speed[2], need_dir[2];               // per series: read by an axis of the group / its speed / its direction
   long long t0, items;                                  // fields t0 .. of this launch; items = fields * items per field
   int ipf;
-  float calm, tan_k[MAXK], scale[MAXC], offset[MAXC];
+  float calm, tan_k[MAXK];
+  HistXform xf;
   JointAxis ax[MAXP][2];
   int off[MAXP];                                        // first cell of the pair's table inside the group
   unsigned long long* counts;                           // the group's slice of counts
 };
-
-template <typename T, int MODE>
-__device__ __forceinline__ void joint_load(const JointSeries& s, int C, long long t, long long i, float (&v)[4][MAXC]) {
-  const T* base = reinterpret_cast<const T*>(s.base);
-  if (MODE == HIST_NCHW4) {
-    const T* q = base + t * s.ld_t + 4 * i;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-      if (c < C) {
-        float w[4];
-        ld4(q + c * s.ld_c, w);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k][c] = w[k];
-      }
-    }
-  } else if (MODE == HIST_PIX16) {
-    const uint4 r = *reinterpret_cast<const uint4*>(base + t * s.ld_t + i * s.ld_p);
-    const unsigned u[4] = {r.x, r.y, r.z, r.w};
-    if (sizeof(T) == 2) {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[0][c] = __uint_as_float(c & 1 ? u[c / 2] & 0xffff0000u : u[c / 2] << 16);
-    } else {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[0][c] = c < 4 ? __uint_as_float(u[c & 3]) : 0.f;
-    }
-  } else {
-    const T* q = base + t * s.ld_t + i * s.ld_p;
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c)
-      if (c < C) v[0][c] = ld_elem(q + c * s.ld_c);
-  }
-}
 
 // the index of one point on one axis (wave-uniform axis): the value is picked by selects, no register array is indexed
 __device__ __forceinline__ int joint_axis_bin(const JointAxis& ax, int C, const float (&y)[2][MAXC], const float (&sp)[2],
@@ -108,8 +72,8 @@ __global__ __launch_bounds__(JOINT_THREADS_MAX) void joint_kernel(JointArgs a) {
     for (int k = 0; k < NPX; ++k)
 #pragma unroll
       for (int c = 0; c < MAXC; ++c) va[k][c] = vb[k][c] = 0.f;
-    if (a.use[0]) joint_load<TA, MODE>(a.s[0], a.C, t, i, va);
-    if (a.use[1]) joint_load<TB, MODE>(a.s[1], a.C, t, i, vb);
+    if (a.use[0]) hist_load_item<TA, MODE>(a.s[0], a.xf.C, t, i, va);
+    if (a.use[1]) hist_load_item<TB, MODE>(a.s[1], a.xf.C, t, i, vb);
     t += dt;
     i += di;
     if (i >= a.ipf) { i -= a.ipf; ++t; }
@@ -122,15 +86,15 @@ __global__ __launch_bounds__(JOINT_THREADS_MAX) void joint_kernel(JointArgs a) {
         float yu = 0.f, yv = 0.f;
 #pragma unroll
         for (int c = 0; c < MAXC; ++c) {
-          y[r][c] = c < a.C ? hist_affine(r ? vb[k][c] : va[k][c], a.scale[c], a.offset[c]) : 0.f;
-          yu = c == a.su ? y[r][c] : yu;
-          yv = c == a.sv ? y[r][c] : yv;
+          y[r][c] = c < a.xf.C ? hist_affine(r ? vb[k][c] : va[k][c], a.xf.scale[c], a.xf.offset[c]) : 0.f;
+          yu = c == a.xf.su ? y[r][c] : yu;
+          yv = c == a.xf.sv ? y[r][c] : yv;
         }
         if (a.need_speed[r]) sp[r] = hist_speed(yu, yv);
         if (a.need_dir[r]) dir[r] = hist_dir(yu, yv, sp[r], a.calm, a.K, a.tan_k);
       }
       for (int p = 0; p < a.npairs; ++p) {
-        const int bx = joint_axis_bin(a.ax[p][0], a.C, y, sp, dir), by = joint_axis_bin(a.ax[p][1], a.C, y, sp, dir);
+        const int bx = joint_axis_bin(a.ax[p][0], a.xf.C, y, sp, dir), by = joint_axis_bin(a.ax[p][1], a.xf.C, y, sp, dir);
         atomicAdd(&joint_lds[a.off[p] + bx * (a.ax[p][1].nbins + 3) + by], 1u);
       }
     }
@@ -142,18 +106,13 @@ __global__ __launch_bounds__(JOINT_THREADS_MAX) void joint_kernel(JointArgs a) {
   }
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 long long cells_of(const dg_hist2d_spec* s, int p) { return (long long)(s->ax[p][0].nbins + 3) * (s->ax[p][1].nbins + 3); }
 
 bool spec_ok(const dg_hist2d_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC || s->npairs < 1 || s->npairs > MAXP) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  if (!finite_f(s->calm) || s->calm < 0.f) return false;
+  if (!s || s->npairs < 1 || s->npairs > MAXP || !hist_xform_ok(s, C)) return false;
+  const bool speed = s->speed_u >= 0;
+  if (!hist_finite(s->calm) || s->calm < 0.f) return false;
   if (s->nsec != 0 && (s->nsec < 4 || s->nsec > DG_HIST2D_MAX_SECTORS || s->nsec % 4 != 0)) return false;
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
   for (int p = 0; p < s->npairs; ++p) {
     for (int e = 0; e < 2; ++e) {
       const dg_hist2d_axis& ax = s->ax[p][e];
@@ -163,7 +122,7 @@ bool spec_ok(const dg_hist2d_spec* s, int C) {
         if (s->nsec == 0 || ax.nbins != s->nsec) return false;
         for (int k = 1; k < s->nsec / 4; ++k)
           if (!(s->tan_k[k] > 0.f && s->tan_k[k] <= FLT_MAX)) return false;
-      } else if (!finite_f(ax.lo) || !(ax.inv_w > 0.f && ax.inv_w <= FLT_MAX)) {
+      } else if (!hist_finite(ax.lo) || !(ax.inv_w > 0.f && ax.inv_w <= FLT_MAX)) {
         return false;
       }
     }
@@ -211,25 +170,18 @@ extern "C" size_t dg_hist2d_ws_bytes(const dg_eof_fields* a, const dg_eof_fields
 
 extern "C" int dg_hist2d_host_bins(const dg_hist2d_spec* s, const float* xa, const float* xb, int C, int64_t n, int32_t* bins) {
   if (!spec_ok(s, C) || n < 0 || (n > 0 && (!xa || !bins)) || (n > 0 && !xb && uses_b(s))) return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  const int K = s->nsec / 4;
+  const int K = s->nsec / 4, nout = hist_nout(s, C);
   for (int64_t i = 0; i < n; ++i) {
-    float y[2][MAXC], sp[2] = {0.f, 0.f}, yu[2] = {0.f, 0.f}, yv[2] = {0.f, 0.f};
-    for (int r = 0; r < 2; ++r) {
-      const float* x = r ? xb : xa;
-      for (int c = 0; c < C; ++c) {
-        y[r][c] = x ? hist_affine(x[(int64_t)c * n + i], s->scale[c], s->offset[c]) : 0.f;
-        if (c == s->speed_u) yu[r] = y[r][c];
-        if (c == s->speed_v) yv[r] = y[r][c];
-      }
-      if (speed) sp[r] = hist_speed(yu[r], yv[r]);
-    }
+    float y[2][HIST_MAXO] = {};                           // every output value of the point, once per series
+    for (int r = 0; r < 2; ++r)
+      if (const float* x = r ? xb : xa)                   // an axis on xb without xb: refused above
+        for (int j = 0; j < nout; ++j) y[r][j] = hist_host_value(s, x, C, (size_t)n, (size_t)i, j);
     for (int p = 0; p < s->npairs; ++p) {
       for (int e = 0; e < 2; ++e) {
         const dg_hist2d_axis& ax = s->ax[p][e];
-        const int r = ax.src;
-        bins[((int64_t)p * 2 + e) * n + i] = ax.chan == C + 1 ? hist_dir(yu[r], yv[r], sp[r], s->calm, K, s->tan_k)
-                                             : hist_bin(ax.chan == C ? sp[r] : y[r][ax.chan], ax.lo, ax.inv_w, ax.nbins);
+        const float* yr = y[ax.src];
+        bins[((int64_t)p * 2 + e) * n + i] = ax.chan == C + 1 ? hist_dir(yr[s->speed_u], yr[s->speed_v], yr[C], s->calm, K, s->tan_k)
+                                                              : hist_bin(yr[ax.chan], ax.lo, ax.inv_w, ax.nbins);
       }
     }
   }
@@ -246,18 +198,12 @@ extern "C" int dg_hist2d(const dg_eof_fields* a, const dg_eof_fields* b, const d
   int mode = hist_mode(a);
   if (two && (hist_mode(b) != mode || b->dtype != a->dtype)) mode = HIST_ANY;
   JointArgs g;
-  g.s[0] = JointSeries{a->base, a->ld_t, a->ld_c, a->ld_p};
-  g.s[1] = JointSeries{fb->base, fb->ld_t, fb->ld_c, fb->ld_p};
-  g.C = a->C;
-  const bool speed = s->speed_u >= 0;
-  g.su = speed ? s->speed_u : -1; g.sv = speed ? s->speed_v : -1;
+  g.s[0] = hist_series(a);
+  g.s[1] = hist_series(fb);
+  g.xf = hist_xform(s, a->C);
   g.K = s->nsec / 4;
   g.calm = s->calm;
   for (int k = 0; k < MAXK; ++k) g.tan_k[k] = k >= 1 && k < g.K ? s->tan_k[k] : 0.f;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < a->C ? s->scale[c] : 1.f;
-    g.offset[c] = c < a->C ? s->offset[c] : 0.f;
-  }
   g.ipf = mode == HIST_NCHW4 ? a->P / 4 : a->P;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   long long done = 0;                                   // cells of the groups before this one

@@ -31,7 +31,7 @@ constexpr int OBJ_THREADS = 256;
 constexpr int OBJ_WAVES = OBJ_THREADS / 64;
 constexpr int OBJ_GRID_T = 4096;                      // fields across gridDim.y at most; the row kernels stride over the rest
 constexpr int OBJ_GRID_PLANES = 16384;                // planes across gridDim.y at most; the plane kernels stride over the rest
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXK = DG_OBJ_MAX_THR, COLS = DG_OBJ_COLS;
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXK = DG_OBJ_MAX_THR, COLS = DG_OBJ_COLS;
 constexpr size_t OBJ_HEADER = 256;                    // bytes in front of the planes: the error word
 constexpr long long QMAX = (1 << 24) - 1;
 
@@ -47,49 +47,16 @@ __host__ __device__ inline long long obj_q(float y, float inv_quantum) {
 }
 
 struct ObjRowArgs {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-  int C, H, W, T, nout, speed, su, sv, nthr, side, paired;
+  HistSeries x;
+  HistXform xf;
+  int H, W, T, nout, nthr, side, paired;
   float inv_quantum;
-  float scale[MAXC], offset[MAXC], thr[MAXO][MAXK];
+  float thr[MAXO][MAXK];
   int* labels;                // plane ((t * 2 + side) * nout + j) * nthr + k, H * W entries each
   const int* slots;           // the same planes: the record slot of every root pixel
   u64* table;
   long long capacity;
 };
-
-// the nout output values of one pixel (q: its channel 0), as fss_values of fss.hip
-template <typename T, int MODE>
-__device__ __forceinline__ void obj_values(const ObjRowArgs& g, const T* q, float (&y)[MAXO]) {
-  float v[MAXC];
-  if (MODE == HIST_PIX16) {
-    const uint4 r = *reinterpret_cast<const uint4*>(q);
-    const unsigned u[4] = {r.x, r.y, r.z, r.w};
-    if (sizeof(T) == 2) {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[c] = __uint_as_float(c & 1 ? u[c / 2] & 0xffff0000u : u[c / 2] << 16);
-    } else {
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) v[c] = c < 4 ? __uint_as_float(u[c & 3]) : 0.f;
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < MAXC; ++c) v[c] = c < g.C ? ld_elem(q + c * g.ld_c) : 0.f;
-  }
-  float yu = 0.f, yv = 0.f;
-#pragma unroll
-  for (int c = 0; c < MAXC; ++c) {
-    y[c] = hist_affine(v[c], g.scale[c], g.offset[c]);
-    yu = c == g.su ? y[c] : yu;
-    yv = c == g.sv ? y[c] : yv;
-  }
-  y[MAXO - 1] = 0.f;
-  if (g.speed) {
-    const float s = hist_speed(yu, yv);
-#pragma unroll
-    for (int j = 0; j < MAXO; ++j) y[j] = j == g.C ? s : y[j];
-  }
-}
 
 template <typename T, int MODE>
 __global__ __launch_bounds__(OBJ_THREADS) void obj_init_kernel(ObjRowArgs g) {
@@ -97,7 +64,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void obj_init_kernel(ObjRowArgs g) {
   const int h = blockIdx.x * OBJ_WAVES + wave;
   if (h >= g.H) return;                                              // wave-uniform
   const long long P = (long long)g.H * g.W;
-  const T* base = reinterpret_cast<const T*>(g.base);
+  const T* base = reinterpret_cast<const T*>(g.x.base);
   const u64 below = (1ull << lane) - 1ull;                           // lanes 0 .. lane - 1
   const int row = h * g.W;
   for (int t = blockIdx.y; t < g.T; t += gridDim.y) {
@@ -112,7 +79,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void obj_init_kernel(ObjRowArgs g) {
       const bool in = w < g.W;
       const long long p = (long long)row + (in ? w : g.W - 1);       // lanes beyond the row read its last pixel, unused
       float y[MAXO];
-      obj_values<T, MODE>(g, base + t * g.ld_t + p * g.ld_p, y);
+      hist_pixel_values<T, MODE>(g.xf, base + t * g.x.ld_t + p * g.x.ld_p, g.x.ld_c, y);
 #pragma unroll
       for (int j = 0; j < MAXO; ++j) {
         if (j < g.nout) {
@@ -229,7 +196,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void obj_stats_kernel(ObjRowArgs g) {
   const int h = blockIdx.x * OBJ_WAVES + wave;
   if (h >= g.H) return;                                              // wave-uniform
   const long long P = (long long)g.H * g.W;
-  const T* base = reinterpret_cast<const T*>(g.base);
+  const T* base = reinterpret_cast<const T*>(g.x.base);
   const u64 upto = ~0ull >> (63 - lane);                             // lanes 0 .. lane
   const int row = h * g.W;
   for (int t = blockIdx.y; t < g.T; t += gridDim.y) {
@@ -242,7 +209,7 @@ __global__ __launch_bounds__(OBJ_THREADS) void obj_stats_kernel(ObjRowArgs g) {
       const bool in = w < g.W;
       const long long p = (long long)row + (in ? w : g.W - 1);
       float y[MAXO];
-      obj_values<T, MODE>(g, base + t * g.ld_t + p * g.ld_p, y);
+      hist_pixel_values<T, MODE>(g.xf, base + t * g.x.ld_t + p * g.x.ld_p, g.x.ld_c, y);
 #pragma unroll
       for (int j = 0; j < MAXO; ++j) {
         if (j < g.nout) {
@@ -309,26 +276,16 @@ __global__ __launch_bounds__(OBJ_THREADS) void obj_stats_kernel(ObjRowArgs g) {
   }
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 bool spec_ok(const dg_objects_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC || s->nthr < 1 || s->nthr > MAXK || (s->connectivity != 4 && s->connectivity != 8)) return false;
-  if (!finite_f(s->inv_quantum) || !(s->inv_quantum > 0.f)) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
-  for (int j = 0; j < nout; ++j)
-    for (int k = 0; k < s->nthr; ++k)
-      if (!finite_f(s->thr[j][k])) return false;
-  return true;
+  if (!s || s->nthr < 1 || s->nthr > MAXK || (s->connectivity != 4 && s->connectivity != 8)) return false;
+  if (!hist_finite(s->inv_quantum) || !(s->inv_quantum > 0.f)) return false;
+  return hist_xform_ok(s, C) && hist_thr_ok(s->thr, hist_nout(s, C), s->nthr);
 }
 
 bool grid_ok(int H, int W) { return H >= 1 && W >= 1 && H <= DG_OBJ_MAX_SIDE && W <= DG_OBJ_MAX_SIDE; }
 
 long long planes_of(const dg_eof_fields* a, const dg_objects_spec* s) {
-  return (long long)a->T * 2 * (a->C + (s->speed_u >= 0 ? 1 : 0)) * s->nthr;
+  return (long long)a->T * 2 * hist_nout(s, a->C) * s->nthr;
 }
 
 bool call_ok(const dg_eof_fields* a, int H, int W, const dg_objects_spec* s) {
@@ -336,23 +293,13 @@ bool call_ok(const dg_eof_fields* a, int H, int W, const dg_objects_spec* s) {
   return planes_of(a, s) * ((a->P + 1) / 2) < (1LL << 31);           // every slot id fits an int32
 }
 
-template <typename T, bool STATS>
-void launch_rows(int mode, const ObjRowArgs& g, dim3 grid, hipStream_t st) {
-  if (STATS) {
-    if (mode == HIST_PIX16) hipLaunchKernelGGL((obj_stats_kernel<T, HIST_PIX16>), grid, dim3(OBJ_THREADS), 0, st, g);
-    else hipLaunchKernelGGL((obj_stats_kernel<T, HIST_ANY>), grid, dim3(OBJ_THREADS), 0, st, g);
-  } else {
-    if (mode == HIST_PIX16) hipLaunchKernelGGL((obj_init_kernel<T, HIST_PIX16>), grid, dim3(OBJ_THREADS), 0, st, g);
-    else hipLaunchKernelGGL((obj_init_kernel<T, HIST_ANY>), grid, dim3(OBJ_THREADS), 0, st, g);
-  }
-}
-
 template <bool STATS>
 void rows_of(const dg_eof_fields* x, int side, ObjRowArgs g, dim3 grid, hipStream_t st) {
-  g.base = x->base; g.ld_t = x->ld_t; g.ld_c = x->ld_c; g.ld_p = x->ld_p; g.side = side;
-  const int mode = hist_mode(x);
-  if (x->dtype == DG_BF16) launch_rows<bf16_t, STATS>(mode, g, grid, st);
-  else launch_rows<float, STATS>(mode, g, grid, st);
+  g.x = hist_series(x); g.side = side;
+  hist_dispatch<false>(x->dtype, hist_mode(x), [&](auto t, auto m) {
+    if (STATS) hipLaunchKernelGGL((obj_stats_kernel<decltype(t), decltype(m)::value>), grid, dim3(OBJ_THREADS), 0, st, g);
+    else hipLaunchKernelGGL((obj_init_kernel<decltype(t), decltype(m)::value>), grid, dim3(OBJ_THREADS), 0, st, g);
+  });
 }
 
 struct HostRec { int64_t v[COLS]; };
@@ -367,8 +314,7 @@ extern "C" size_t dg_objects_ws_bytes(const dg_eof_fields* a, int H, int W, cons
 extern "C" int dg_objects_host(const dg_objects_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* table,
                                int64_t capacity, int64_t* count, int64_t* per_plane) {
   if (!spec_ok(s, C) || !a || !count || !per_plane || !grid_ok(H, W) || capacity < 0 || (capacity > 0 && !table)) return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  const int nout = C + (speed ? 1 : 0), conn8 = s->connectivity == 8;
+  const int nout = hist_nout(s, C), conn8 = s->connectivity == 8;
   const size_t P = (size_t)H * W;
   const float* x[2] = {a, b};
   std::vector<float> y[2];
@@ -381,15 +327,7 @@ extern "C" int dg_objects_host(const dg_objects_spec* s, const float* a, const f
       for (int e = 0; e < 2; ++e) {                                  // the values of channel j of both sides
         if (!x[e]) continue;
         y[e].resize(P);
-        for (size_t p = 0; p < P; ++p) {
-          if (j < C) {
-            y[e][p] = hist_affine(x[e][j * P + p], s->scale[j], s->offset[j]);
-          } else {
-            const int u = s->speed_u, v = s->speed_v;
-            y[e][p] = hist_speed(hist_affine(x[e][u * P + p], s->scale[u], s->offset[u]),
-                                 hist_affine(x[e][v * P + p], s->scale[v], s->offset[v]));
-          }
-        }
+        for (size_t p = 0; p < P; ++p) y[e][p] = hist_host_value(s, x[e], C, P, p, j);
       }
       for (int k = 0; k < s->nthr; ++k) {
         for (int e = 0; e < 2; ++e) {
@@ -451,7 +389,7 @@ extern "C" int dg_objects(const dg_eof_fields* a, const dg_eof_fields* b, int H,
   if ((a->dtype != DG_F32 && a->dtype != DG_BF16) || (b && b->dtype != DG_F32 && b->dtype != DG_BF16)) return DG_ERR_BAD_DTYPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long long nplanes = planes_of(a, s), P = a->P;
-  const int nout = a->C + (s->speed_u >= 0 ? 1 : 0);
+  const int nout = hist_nout(s, a->C);
   int* err = reinterpret_cast<int*>(ws);
   int* labels = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + OBJ_HEADER);
   int* slots = labels + nplanes * P;
@@ -462,15 +400,10 @@ extern "C" int dg_objects(const dg_eof_fields* a, const dg_eof_fields* b, int H,
   if (!b && hipMemsetAsync(labels, 0xff, (size_t)nplanes * P * sizeof(int), st) != hipSuccess) return DG_ERR_LAUNCH;
 
   ObjRowArgs g;
-  g.C = a->C; g.H = H; g.W = W; g.T = a->T; g.nout = nout; g.nthr = s->nthr; g.paired = b ? 1 : 0;
-  g.speed = s->speed_u >= 0 ? 1 : 0; g.su = g.speed ? s->speed_u : -1; g.sv = g.speed ? s->speed_v : -1;
+  g.xf = hist_xform(s, a->C);
+  g.H = H; g.W = W; g.T = a->T; g.nout = nout; g.nthr = s->nthr; g.paired = b ? 1 : 0;
   g.inv_quantum = s->inv_quantum;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < a->C ? s->scale[c] : 1.f;
-    g.offset[c] = c < a->C ? s->offset[c] : 0.f;
-  }
-  for (int j = 0; j < MAXO; ++j)
-    for (int k = 0; k < MAXK; ++k) g.thr[j][k] = j < nout && k < s->nthr ? s->thr[j][k] : INFINITY;
+  hist_thr_pad(s->thr, nout, s->nthr, g.thr);
   g.labels = labels; g.slots = slots; g.table = reinterpret_cast<u64*>(table); g.capacity = capacity;
   const unsigned gt = (unsigned)(a->T < OBJ_GRID_T ? a->T : OBJ_GRID_T);
   const dim3 rgrid((unsigned)((H + OBJ_WAVES - 1) / OBJ_WAVES), gt);

@@ -31,17 +31,16 @@ namespace {
 constexpr int TP_THREADS = 256;
 constexpr int TP_TMAX = 1 << 20;                      // fields per launch: 256 threads * 4 pixels * 2^20 adds < 2^32 per LDS cell
 constexpr long long TP_QUAD_MIN_ITEMS = 65536;        // four pixels per thread only where P / 4 still gives every CU a workgroup
-constexpr int MAXC = DG_EOF_MAX_C, MAXO = DG_HIST_MAX_OUT, MAXK = DG_TEMPORAL_MAX_THR, MAXL = DG_TEMPORAL_MAX_LAGS;
+constexpr int MAXO = DG_HIST_MAX_OUT, MAXK = DG_TEMPORAL_MAX_THR, MAXL = DG_TEMPORAL_MAX_LAGS;
 constexpr int MAXB3 = DG_TEMPORAL_MAX_BINS + 3, MAXD = DG_TEMPORAL_MAX_DUR;
 
 struct TpArgs {
-  const void* base;
-  long long ld_t, ld_c, ld_p;
-  int C, P, T, su, sv;
+  HistSeries x;
+  HistXform xf;
+  int P, T;
   int nthr, ndur, nlag, nbins, R;
   int t0, slot0;                                      // the absolute time of the launch's first field; t0 mod R
   int below[MAXK], lag[MAXL];
-  float scale[MAXC], offset[MAXC];
   float thr[MAXO][MAXK], lo[MAXO][MAXL], inv_w[MAXO][MAXL];
   // the arrays of this launch's series
   int* open;
@@ -53,8 +52,6 @@ struct TpArgs {
   int* accnt;
 };
 
-__host__ __device__ inline bool tp_finite(float v) { return __builtin_fabsf(v) <= FLT_MAX; }   // false for NaN and +-inf
-
 // the loads of one field for this thread's pixels: the raw input, or (from the tail ring) y itself in x1
 template <int MODE, bool SPD> struct TpRaw {
   static constexpr int NPX = MODE == HIST_NCHW4 ? 4 : 1;
@@ -62,27 +59,18 @@ template <int MODE, bool SPD> struct TpRaw {
 };
 template <bool SPD> struct TpRaw<HIST_PIX16, SPD> { uint4 r; };
 
-// channel c (wave-uniform) of a pixel loaded as 16 bytes: selects, no register array to index
-template <typename T>
-__device__ __forceinline__ float tp_pick(const uint4& r, int c) {
-  const int w = sizeof(T) == 2 ? c >> 1 : c;
-  const unsigned word = w == 0 ? r.x : w == 1 ? r.y : w == 2 ? r.z : r.w;
-  if (sizeof(T) == 2) return __uint_as_float(c & 1 ? word & 0xffff0000u : word << 16);
-  return __uint_as_float(word);
-}
-
 // field tl (index within the launch) of this thread's pixels (i: pixel quad in HIST_NCHW4, else pixel)
 template <typename T, int MODE, bool SPD>
 __device__ __forceinline__ void tp_load(const TpArgs& g, long long tl, long long i, int c1, int c2, TpRaw<MODE, SPD>& r) {
-  const T* base = reinterpret_cast<const T*>(g.base) + tl * g.ld_t;
+  const T* base = reinterpret_cast<const T*>(g.x.base) + tl * g.x.ld_t;
   if constexpr (MODE == HIST_NCHW4) {
-    ld4(base + c1 * g.ld_c + 4 * i, r.x1);
-    if constexpr (SPD) ld4(base + c2 * g.ld_c + 4 * i, r.x2);
+    ld4(base + c1 * g.x.ld_c + 4 * i, r.x1);
+    if constexpr (SPD) ld4(base + c2 * g.x.ld_c + 4 * i, r.x2);
   } else if constexpr (MODE == HIST_PIX16) {
-    r.r = *reinterpret_cast<const uint4*>(base + i * g.ld_p);
+    r.r = *reinterpret_cast<const uint4*>(base + i * g.x.ld_p);
   } else {
-    r.x1[0] = ld_elem(base + c1 * g.ld_c + i * g.ld_p);
-    if constexpr (SPD) r.x2[0] = ld_elem(base + c2 * g.ld_c + i * g.ld_p);
+    r.x1[0] = ld_elem(base + c1 * g.x.ld_c + i * g.x.ld_p);
+    if constexpr (SPD) r.x2[0] = ld_elem(base + c2 * g.x.ld_c + i * g.x.ld_p);
   }
 }
 
@@ -105,8 +93,8 @@ __device__ __forceinline__ float tp_value(const TpRaw<MODE, SPD>& r, int q, bool
   float x1, x2;
   if constexpr (MODE == HIST_PIX16) {
     if (ring) return __uint_as_float(r.r.x);
-    x1 = tp_pick<T>(r.r, x.c1);
-    x2 = SPD ? tp_pick<T>(r.r, x.c2) : x1;
+    x1 = hist_pick16_sel<T>(r.r, x.c1);
+    x2 = SPD ? hist_pick16_sel<T>(r.r, x.c2) : x1;
   } else {
     if (ring) return r.x1[q];
     x1 = r.x1[q];
@@ -127,14 +115,14 @@ __global__ __launch_bounds__(TP_THREADS) void temporal_kernel(TpArgs g) {
   for (int i = tid; i < g.nthr * g.ndur; i += TP_THREADS) lds_spells[i] = 0u;
   __syncthreads();
 
-  const int j = SPD ? g.C : (int)blockIdx.y;          // the output channel of this workgroup
+  const int j = SPD ? g.xf.C : (int)blockIdx.y;          // the output channel of this workgroup
   const long long P = g.P, i = (long long)blockIdx.x * TP_THREADS + tid, p0 = i * NPX;
   if (i < P / NPX) {
     TpXf xf;
-    xf.c1 = SPD ? g.su : j;
-    xf.c2 = SPD ? g.sv : j;
-    xf.sc1 = g.scale[xf.c1]; xf.of1 = g.offset[xf.c1];
-    xf.sc2 = g.scale[xf.c2]; xf.of2 = g.offset[xf.c2];
+    xf.c1 = SPD ? g.xf.su : j;
+    xf.c2 = SPD ? g.xf.sv : j;
+    xf.sc1 = g.xf.scale[xf.c1]; xf.of1 = g.xf.offset[xf.c1];
+    xf.sc2 = g.xf.scale[xf.c2]; xf.of2 = g.xf.offset[xf.c2];
     float thr[MAXK], lo[MAXL], inv_w[MAXL];
 #pragma unroll
     for (int k = 0; k < MAXK; ++k) thr[k] = g.thr[j][k];
@@ -200,7 +188,7 @@ __global__ __launch_bounds__(TP_THREADS) void temporal_kernel(TpArgs g) {
 #pragma unroll
           for (int q = 0; q < NPX; ++q) {
             const float y = tp_value<T, MODE, SPD>(cur[u], q, false, xf);
-            const bool fin = tp_finite(y);
+            const bool fin = hist_finite(y);
             const double yd = (double)y;
 #pragma unroll
             for (int k = 0; k < MAXK; ++k) {
@@ -225,7 +213,7 @@ __global__ __launch_bounds__(TP_THREADS) void temporal_kernel(TpArgs g) {
                 const float yl = tp_value<T, MODE, SPD>(par[u][l], q, t - g.lag[l] < 0, xf);
                 const float d = hist_diff(y, yl);
                 atomicAdd(&lds_ramps[l * nb3 + hist_bin(d, lo[l], inv_w[l], g.nbins)], 1u);
-                const bool both = fin && tp_finite(yl);
+                const bool both = fin && hist_finite(yl);
                 const double yld = (double)yl;
                 m[l][q] += both ? 1 : 0;
                 cs[l][q] = both ? cs[l][q] + yd * yld : cs[l][q];
@@ -276,28 +264,19 @@ __global__ __launch_bounds__(TP_THREADS) void temporal_kernel(TpArgs g) {
   }
 }
 
-bool finite_f(float v) { return fabsf(v) <= FLT_MAX; }
-
 bool spec_ok(const dg_temporal_spec* s, int C) {
-  if (!s || C < 1 || C > MAXC) return false;
+  if (!s || !hist_xform_ok(s, C)) return false;
   if (s->nthr < 0 || s->nthr > MAXK || s->nlag < 0 || s->nlag > MAXL || (s->nthr == 0 && s->nlag == 0)) return false;
   if (s->ndur < 1 || s->ndur > MAXD || s->nbins < 1 || s->nbins > DG_TEMPORAL_MAX_BINS) return false;
-  const bool speed = s->speed_u >= 0 || s->speed_v >= 0;
-  if (speed && (s->speed_u < 0 || s->speed_u >= C || s->speed_v < 0 || s->speed_v >= C)) return false;
   for (int k = 0; k < s->nthr; ++k)
     if (s->below[k] != 0 && s->below[k] != 1) return false;
   for (int l = 0; l < s->nlag; ++l)
     if (s->lag[l] < 1 || s->lag[l] > DG_TEMPORAL_MAX_LAG || (l > 0 && s->lag[l] <= s->lag[l - 1])) return false;
-  for (int c = 0; c < C; ++c)
-    if (!finite_f(s->scale[c]) || !finite_f(s->offset[c])) return false;
-  const int nout = C + (speed ? 1 : 0);
-  for (int j = 0; j < nout; ++j) {
-    for (int k = 0; k < s->nthr; ++k)
-      if (!finite_f(s->thr[j][k])) return false;
+  const int nout = hist_nout(s, C);
+  for (int j = 0; j < nout; ++j)
     for (int l = 0; l < s->nlag; ++l)
-      if (!finite_f(s->lo[j][l]) || !(s->inv_w[j][l] > 0.f && s->inv_w[j][l] <= FLT_MAX)) return false;
-  }
-  return true;
+      if (!hist_finite(s->lo[j][l]) || !(s->inv_w[j][l] > 0.f && s->inv_w[j][l] <= FLT_MAX)) return false;
+  return hist_thr_ok(s->thr, nout, s->nthr);
 }
 
 bool time_ok(int64_t t0, int T) { return t0 >= 0 && t0 + (int64_t)T < ((int64_t)1 << 31); }
@@ -322,15 +301,8 @@ void launch_mode(const TpArgs& g, bool speed, hipStream_t st) {
   constexpr int NPX = MODE == HIST_NCHW4 ? 4 : 1;
   const long long items = g.P / NPX;
   const unsigned nbx = (unsigned)((items + TP_THREADS - 1) / TP_THREADS);
-  hipLaunchKernelGGL((temporal_kernel<T, MODE, false>), dim3(nbx, (unsigned)g.C), dim3(TP_THREADS), 0, st, g);
+  hipLaunchKernelGGL((temporal_kernel<T, MODE, false>), dim3(nbx, (unsigned)g.xf.C), dim3(TP_THREADS), 0, st, g);
   if (speed) hipLaunchKernelGGL((temporal_kernel<T, MODE, true>), dim3(nbx, 1), dim3(TP_THREADS), 0, st, g);
-}
-
-template <typename T>
-void launch_type(int mode, const TpArgs& g, bool speed, hipStream_t st) {
-  if (mode == HIST_NCHW4) launch_mode<T, HIST_NCHW4>(g, speed, st);
-  else if (mode == HIST_PIX16) launch_mode<T, HIST_PIX16>(g, speed, st);
-  else launch_mode<T, HIST_ANY>(g, speed, st);
 }
 
 }  // namespace
@@ -347,19 +319,15 @@ extern "C" int dg_temporal(const dg_eof_fields* a, const dg_eof_fields* b, const
   if (!dtype_ok(a) || (b && !dtype_ok(b))) return DG_ERR_BAD_DTYPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool speed = s->speed_u >= 0;
-  const long long C = a->C, P = a->P, nout = C + (speed ? 1 : 0), nb3 = s->nbins + 3;
+  const long long P = a->P, nout = hist_nout(s, a->C), nb3 = s->nbins + 3;
   const int R = s->nlag > 0 ? s->lag[s->nlag - 1] : 0;
 
   TpArgs g;
-  g.C = a->C; g.P = a->P;
-  g.su = speed ? s->speed_u : 0; g.sv = speed ? s->speed_v : 0;
+  g.xf = hist_xform(s, a->C);
+  g.P = a->P;
   g.nthr = s->nthr; g.ndur = s->ndur; g.nlag = s->nlag; g.nbins = s->nbins; g.R = R;
   for (int k = 0; k < MAXK; ++k) g.below[k] = k < s->nthr ? s->below[k] : 0;
   for (int l = 0; l < MAXL; ++l) g.lag[l] = l < s->nlag ? s->lag[l] : 0;
-  for (int c = 0; c < MAXC; ++c) {
-    g.scale[c] = c < C ? s->scale[c] : 1.f;
-    g.offset[c] = c < C ? s->offset[c] : 0.f;
-  }
   for (int j = 0; j < MAXO; ++j) {
     for (int k = 0; k < MAXK; ++k) g.thr[j][k] = j < nout && k < s->nthr ? s->thr[j][k] : 0.f;
     for (int l = 0; l < MAXL; ++l) {
@@ -370,7 +338,7 @@ extern "C" int dg_temporal(const dg_eof_fields* a, const dg_eof_fields* b, const
   }
   for (int ser = 0; ser < (b ? 2 : 1); ++ser) {
     const dg_eof_fields* x = ser ? b : a;
-    g.ld_t = x->ld_t; g.ld_c = x->ld_c; g.ld_p = x->ld_p;
+    g.x = hist_series(x);
     // the arrays of this series (a NULL array is never touched: its nthr / nlag is 0)
     g.open = open ? open + ser * nout * s->nthr * P : nullptr;
     g.tail = tail ? tail + ser * nout * R * P : nullptr;
@@ -384,12 +352,11 @@ extern "C" int dg_temporal(const dg_eof_fields* a, const dg_eof_fields* b, const
     if (mode == HIST_NCHW4 && P / 4 < TP_QUAD_MIN_ITEMS) mode = HIST_ANY;
     const size_t es = x->dtype == DG_F32 ? 4 : 2;
     for (long long tt = 0; tt < x->T; tt += TP_TMAX) {
-      g.base = static_cast<const char*>(x->base) + (size_t)tt * (size_t)x->ld_t * es;
+      g.x.base = static_cast<const char*>(x->base) + (size_t)tt * (size_t)x->ld_t * es;
       g.T = (int)(x->T - tt < TP_TMAX ? x->T - tt : TP_TMAX);
       g.t0 = (int)(t0 + tt);
       g.slot0 = R > 0 ? (int)((t0 + tt) % R) : 0;
-      if (x->dtype == DG_F32) launch_type<float>(mode, g, speed, st);
-      else launch_type<bf16_t>(mode, g, speed, st);
+      hist_dispatch(x->dtype, mode, [&](auto t, auto m) { launch_mode<decltype(t), decltype(m)::value>(g, speed, st); });
     }
   }
   return dg_check_launch();
@@ -399,8 +366,7 @@ extern "C" int dg_temporal_host(const dg_temporal_spec* s, const float* x, int C
                                 float* tail, int64_t* spells, int32_t* spellmap, int64_t* ramps, double* acsum, int32_t* accnt) {
   if (!spec_ok(s, C) || T < 1 || P < 1 || !x || !time_ok(t0, T) || !arrays_ok(s, open, tail, spells, spellmap, ramps, acsum, accnt))
     return DG_ERR_BAD_SHAPE;
-  const bool speed = s->speed_u >= 0;
-  const int nout = C + (speed ? 1 : 0), nb3 = s->nbins + 3, nthr = s->nthr, nlag = s->nlag;
+  const int nout = hist_nout(s, C), nb3 = s->nbins + 3, nthr = s->nthr, nlag = s->nlag;
   const int R = nlag > 0 ? s->lag[nlag - 1] : 0;
   const size_t Pl = (size_t)P;
   // y of the times t0 - R .. t0 + T - 1 of one output channel and pixel: the ring's part, then this call's
@@ -409,15 +375,7 @@ extern "C" int dg_temporal_host(const dg_temporal_spec* s, const float* x, int C
     for (size_t p = 0; p < Pl; ++p) {
       for (int64_t ta = t0 - R; ta < t0; ++ta)
         y[(size_t)(ta - (t0 - R))] = ta >= 0 ? tail[((size_t)j * R + (size_t)(ta % R)) * Pl + p] : 0.f;
-      for (int t = 0; t < T; ++t) {
-        const float* f = x + (size_t)t * C * Pl + p;
-        if (j < C) {
-          y[(size_t)R + t] = hist_affine(f[j * Pl], s->scale[j], s->offset[j]);
-        } else {
-          const int u = s->speed_u, v = s->speed_v;
-          y[(size_t)R + t] = hist_speed(hist_affine(f[u * Pl], s->scale[u], s->offset[u]), hist_affine(f[v * Pl], s->scale[v], s->offset[v]));
-        }
-      }
+      for (int t = 0; t < T; ++t) y[(size_t)R + t] = hist_host_value(s, x + (size_t)t * C * Pl, C, Pl, p, j);
       double* sums = acsum + (size_t)j * (2 + 2 * nlag) * Pl + p;
       int32_t* cnt = accnt + (size_t)j * (1 + nlag) * Pl + p;
       for (int t = 0; t < T; ++t) {
@@ -436,7 +394,7 @@ extern "C" int dg_temporal_host(const dg_temporal_spec* s, const float* x, int C
             *run = 0;
           }
         }
-        const bool fin = tp_finite(yt);
+        const bool fin = hist_finite(yt);
         const double yd = (double)yt;
         if (fin) {
           cnt[0] += 1;
@@ -448,7 +406,7 @@ extern "C" int dg_temporal_host(const dg_temporal_spec* s, const float* x, int C
           const float yl = y[(size_t)R + t - s->lag[l]];
           const float d = hist_diff(yt, yl);
           ramps[((size_t)j * nlag + l) * nb3 + hist_bin(d, s->lo[j][l], s->inv_w[j][l], s->nbins)] += 1;
-          if (fin && tp_finite(yl)) {
+          if (fin && hist_finite(yl)) {
             const double yld = (double)yl;
             cnt[(1 + l) * Pl] += 1;
             sums[(2 + 2 * l) * Pl] += yd * yld;
