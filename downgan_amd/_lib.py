@@ -161,6 +161,8 @@ _PROTOS = {
     "dg_conv3x3_plan": [C.POINTER(ConvGeom), _i, C.POINTER(GGDesc)],
     "dg_last_conv_kernels": [],
     "dg_conv3x3_dgrad_launches": [C.POINTER(ConvGeom)],
+    "dg_conv3x3_dgrad_stream_eligible": [C.POINTER(ConvGeom), C.POINTER(Epilogue)],
+    "dg_set_s2_dgrad_stream": [C.c_int],
     "dg_colsum": [_i, _vp, _i64, _i64, _i64, _i64, _i, _vp, _vp],
     "dg_colsum_multi": [_i, _vp, _i64, _i64, _i, _i, _vp, _vp],
     "dg_repack_conv_weights": [_i, _i, _vp, _vp, _i, _i, _vp],

@@ -259,6 +259,9 @@ extern "C" int dg_conv3x3_dgrad(const dg_conv_geom* g, const dg_epilogue* ep, co
   g_last_kinds = 0;
   int n = dg_conv3x3_plan(g, 1, d);
   if (n < 0) return n;
+  // the 128 -> 128 channel stride-2 layer in bf16 with a plain or mask_bits epilogue: weights stay on the CU, dy streams (conv_s2dgrad.hip)
+  if (s2dgrad_stream_mode() && s2dgrad_stream_eligible(g, ep))
+    return s2dgrad_stream_launch(g, ep, dy, w_dgrad, dx, reinterpret_cast<hipStream_t>(stream));
   dg_gg_desc ds;
   if (seg_dgrad_desc(d, n, &ds)) return gather_gemm_impl(&ds, ep, dy, w_dgrad, dx, stream, false, nullptr, true);
   for (int i = 0; i < n; ++i) {
@@ -299,6 +302,14 @@ extern "C" int dg_conv3x3_dgrad_f8(const dg_conv_geom* g, const dg_epilogue* ep,
 }
 
 extern "C" int dg_last_conv_kernels(void) { return g_last_kinds; }
+
+// Host-side probe (no GPU): would dg_conv3x3_dgrad(g, ep, ...) run on the streaming kernel of conv_s2dgrad.hip while its switch is
+// on -- 1 / 0, < 0 = dg_status of a geometry the planner refuses.
+extern "C" int dg_conv3x3_dgrad_stream_eligible(const dg_conv_geom* g, const dg_epilogue* ep) {
+  const int rc = geom_validate(g);
+  if (rc) return rc;
+  return s2dgrad_stream_eligible(g, ep) ? 1 : 0;
+}
 
 // Host-side probe of the planner (no GPU): how a stride-2 data gradient of geometry `g` would be launched --
 // 1 = one merged launch of the halo kernel (conv_halo.hip, SEG), 4 = one launch per parity class, < 0 = dg_status.

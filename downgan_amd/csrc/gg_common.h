@@ -24,6 +24,7 @@
 //   conv_rows.hip     gg_kernel / gg_fast_kernel   row-tiled gather-GEMM (any shape; pixel-shuffled sources, narrow layers)
 //   conv_halo.hip     gg_halo4w_kernel             16x16-pixel tiles with the source patch resident in LDS (the dominant kernel)
 //   conv_halo_f8.hip  gg_halo4w_f8_kernel          the same on the block-scaled MXFP8 MFMA
+//   conv_s2dgrad.hip  s2dgrad_stream_kernel        weight-stationary stride-2 data gradient of the 128 -> 128 channel layer (bf16)
 //   conv_small.hip    gg_halo16_kernel, gg_im2col_kernel, gg_im2col_direct_kernel   <= 16 output / <= 2 real input channels (HBM-bound)
 //   conv_plan.hip     host side: lowering of a conv layer to descriptors, kernel choice, the C ABI entry points
 #pragma once
@@ -34,7 +35,7 @@
 
 
 // bit mask of the kernel variants the last dg_conv3x3_fwd / _dgrad call of this thread launched (bench.py tags its
-// live timings with it): 1 generic, 2 fast, 8 halo, 16 im2col, 32 fp8 halo (defined in conv_plan.hip)
+// live timings with it): 1 generic, 2 fast, 8 halo, 16 im2col, 32 fp8 halo, 64 stride-2 data-gradient stream (defined in conv_plan.hip)
 extern thread_local int g_last_kinds;
 
 struct GGArgs {
@@ -625,3 +626,7 @@ int gg_launch_halo(GGArgs& a, int dtype, int N, bool s2, bool ps, int nw, hipStr
 int gg_launch_halo_f8(GGArgs& a, const F8Args& f, int N, bool s2, int nw, hipStream_t st);
 int gg_launch_halo16(GGArgs& a, int dtype, int N, hipStream_t st);
 int gg_launch_im2col(GGArgs& a, int dtype, hipStream_t st);
+// conv_s2dgrad.hip: the rule, the process-wide switch (0 off, 1 on, n > 1 on with at most n workgroups) and the launch
+bool s2dgrad_stream_eligible(const dg_conv_geom* g, const dg_epilogue* ep);
+int s2dgrad_stream_mode();
+int s2dgrad_stream_launch(const dg_conv_geom* g, const dg_epilogue* ep, const void* dy, const void* w, void* dx, hipStream_t st);

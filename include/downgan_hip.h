@@ -188,7 +188,8 @@ int dg_gather_gemm(const dg_gg_desc* d, const dg_epilogue* ep, const void* x, co
                    void* stream);
 
 /* Which kernel variants the calling thread's last dg_conv3x3_fwd / _dgrad launched (bit mask: 1 generic
- * gather-GEMM, 2 fast path, 8 halo-patch kernel, 16 im2col small-Cin kernel). Diagnostic. */
+ * gather-GEMM, 2 fast path, 8 halo-patch kernel, 16 im2col small-Cin kernel, 32 fp8 halo kernel, 64 streaming stride-2
+ * data-gradient kernel). Diagnostic. */
 int dg_last_conv_kernels(void);
 
 /* Host-only planner (no GPU needed): lowers a layer to its gather-GEMM descriptor(s).
@@ -200,6 +201,18 @@ int dg_conv3x3_plan(const dg_conv_geom* g, int kind, dg_gg_desc* out);
  * of the halo kernel (or a stride-1 layer's single class), 4 = one launch per class (narrow layers, or rows too long for the halo
  * kernel's 24-bit row step), negative = dg_status. */
 int dg_conv3x3_dgrad_launches(const dg_conv_geom* g);
+
+/* Host-only: 1 if dg_conv3x3_dgrad(g, ep, ...) takes the weight-stationary streaming kernel (one launch; all nine taps stay in
+ * the registers of one workgroup per CU while dy streams through; bit-identical to the merged halo launch), else 0; negative =
+ * dg_status.  The rule: bf16, stride 2, Cin = Cout = 128 with dense pixels (ldx = ldy = 128), no pixel shuffle; an epilogue that
+ * is absent, plain, or mask_bits + mask_slope only; a dy row within the halo kernel's row-step limit (W/2 * 256 B < 8 MiB) and an
+ * image of dx below 2 GiB.  ep may be NULL. */
+int dg_conv3x3_dgrad_stream_eligible(const dg_conv_geom* g, const dg_epilogue* ep);
+
+/* Process-wide A/B switch of that kernel: 0 = every stride-2 data gradient on the halo kernel, 1 = eligible calls stream
+ * (default), n > 1 = as 1 with the launch capped at n workgroups (tests of the persistent walk at small shapes).  Negative
+ * values count as 0.  Returns the previous value. */
+int dg_set_s2_dgrad_stream(int on);
 
 /* Derives the compute-precision weight packs from the fp32 MASTER, which is kept forward-packed and
  * padded as [CoutP][9][CinP] (tap = r*3+s; for a pixel-shuffle layer the host has already moved
