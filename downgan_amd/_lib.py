@@ -160,6 +160,7 @@ _PROTOS = {
     "dg_gather_gemm": [C.POINTER(GGDesc), C.POINTER(Epilogue), _vp, _vp, _vp, _vp],
     "dg_conv3x3_plan": [C.POINTER(ConvGeom), _i, C.POINTER(GGDesc)],
     "dg_last_conv_kernels": [],
+    "dg_last_wgrad_kernel": [],
     "dg_conv3x3_dgrad_launches": [C.POINTER(ConvGeom)],
     "dg_conv3x3_dgrad_stream_eligible": [C.POINTER(ConvGeom), C.POINTER(Epilogue)],
     "dg_set_s2_dgrad_stream": [C.c_int],

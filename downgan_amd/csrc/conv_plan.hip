@@ -112,6 +112,8 @@ static int gather_gemm_impl(const dg_gg_desc* d, const dg_epilogue* ep, const vo
     a.mask = ep->mask; a.ldmask = ep->ldmask; a.mask_slope = ep->mask_slope;
     a.mask_c0 = ep->mask_c0; a.mask_last = ep->mask_last;
     if (a.mask_c0 < 0 || a.mask_c0 % 16 || ((a.mask_c0 || a.mask_last) && !a.mask)) return DG_ERR_BAD_ARG;
+    // the kernels compare the PACKED output channel with mask_c0; behind a pixel shuffle that is not the destination's channel
+    if (a.mask_c0 && d->dst_ps) return DG_ERR_BAD_SHAPE;
     a.accumulate = ep->accumulate;
     a.mask_bits = ep->mask_bits; a.out_bits = ep->out_bits;
     a.out_q = ep->out_q; a.out_qs = ep->out_qs;

@@ -365,6 +365,12 @@ __global__ __launch_bounds__(256) void wg_kernel(const WGArgs a) {
     }
 }
 
+// Which launcher served the calling thread's last dg_conv3x3_wgrad* call (dg_last_wgrad_kernel; codes in include/downgan_hip.h):
+// host-side bookkeeping, reset at the entry points and written by each launcher.
+enum { WGK_NONE = 0, WGK_TAP = 1, WGK_IM2COL = 2, WGK_ROWS = 3, WGK_WIDE_S1 = 4, WGK_WIDE_S2 = 5, WGK_DENSE = 6, WGK_F8 = 7 };
+static thread_local int g_last_wgrad = WGK_NONE;
+extern "C" int dg_last_wgrad_kernel(void) { return g_last_wgrad; }
+
 // Split-K factor of a weight-gradient launch: ntiles x splits workgroups, the LARGEST count that still fits `target` (a whole
 // number of rounds of the chip's resident-workgroup slots, or the atomics budget `cap` if that is smaller).  Rounding the
 // split count up instead spilled a few workgroups into an extra, nearly empty round (96 tiles x 22 splits = 2112 = 4.125
@@ -423,6 +429,7 @@ static int wg_resident(K kernel, int lds_bytes) {
 
 template <typename T>
 static int wg_launch_im2col(WGArgs& a, hipStream_t st) {
+  g_last_wgrad = WGK_IM2COL;
   const bool big_co = a.Cout > 64;
   const int bco = big_co ? 128 : 64;
   const int nco_t = (a.Cout + bco - 1) / bco;
@@ -454,6 +461,7 @@ static int wg_launch_im2col(WGArgs& a, hipStream_t st) {
 
 template <typename T>
 static int wg_launch(WGArgs& a, hipStream_t st) {
+  g_last_wgrad = WGK_TAP;
   const bool big_co = a.Cout > 64, big_ci = a.Cin > 64;
   const int bco = big_co ? 128 : 64, bci = big_ci ? 128 : 64;
   const int nco_t = (a.Cout + bco - 1) / bco;
@@ -696,6 +704,7 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
 
 template <typename T>
 static int wg3_launch(WGArgs& a, hipStream_t st) {
+  g_last_wgrad = WGK_ROWS;
   constexpr int BCO = 64, BCI = 128;
   const int nco_t = (a.Cout + BCO - 1) / BCO;
   a.nci_t = (a.Cin + BCI - 1) / BCI;
@@ -945,6 +954,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
 
 template <bool S2>
 static int wg3w_launch(WGArgs& a, hipStream_t st) {
+  g_last_wgrad = a.tri ? WGK_DENSE : S2 ? WGK_WIDE_S2 : WGK_WIDE_S1;
   constexpr int BCO = 128, BCI = 128;
   const int nco_t = (a.Cout + BCO - 1) / BCO;
   a.nci_t = (a.Cin + BCI - 1) / BCI;
@@ -1158,6 +1168,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
 
 // launch of the fp8 kernel for a prepared WGArgs (x / u / ex / eu / geometry / Mpix set; tri + dwk[] in dense-block mode)
 static int wg3w_f8_launch(WGArgs& a, hipStream_t st) {
+  g_last_wgrad = WGK_F8;
   constexpr int BCO = 128, BCI = 128;
   const int nco_t = a.Cout / BCO;
   a.nci_t = a.Cin / BCI;
@@ -1188,6 +1199,7 @@ static int wg3w_f8_launch(WGArgs& a, hipStream_t st) {
 // exponents: x = xq * 2^(ex[ci / 32] - 127), dy = dyq * 2^(ey[co / 32] - 127) (`ldx` / `ldy` of g = pixel strides in bytes).
 extern "C" int dg_conv3x3_wgrad_f8(const dg_conv_geom* g, const void* xq, const void* ex, const void* dyq, const void* ey, float* dw,
                                    void* stream) {
+  g_last_wgrad = WGK_NONE;
   if (!g || !xq || !ex || !dyq || !ey || !dw) return DG_ERR_BAD_ARG;
   if (g->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;               // (the dtype of the tensors the fp8 forms stand for)
   if (g->N <= 0 || g->H <= 0 || g->W <= 0 || (g->stride != 1 && g->stride != 2) || g->pixel_shuffle) return DG_ERR_BAD_SHAPE;
@@ -1210,6 +1222,7 @@ extern "C" int dg_conv3x3_wgrad_f8(const dg_conv_geom* g, const void* xq, const 
 // gradients only (the bias gradients are column sums of the adjoint: dg_colsum).  W % 64 == 0.
 extern "C" int dg_conv3x3_wgrad_dense_f8(const dg_conv_geom* g, int nconv, const void* xq, const void* ex, const void* dyq, const void* ey,
                                          float* const* dw, void* stream) {
+  g_last_wgrad = WGK_NONE;
   if (!g || !xq || !ex || !dyq || !ey || !dw) return DG_ERR_BAD_ARG;
   if (g->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
   if (nconv < 1 || nconv > 8 || g->N <= 0 || g->H <= 0 || g->W <= 0 || g->stride != 1 || g->pixel_shuffle || g->W % 64) return DG_ERR_BAD_SHAPE;
@@ -1233,6 +1246,7 @@ extern "C" int dg_colsum(int dtype, const void* dy, int64_t rows_outer, int64_t 
                          float* db, void* stream);
 
 extern "C" int dg_conv3x3_wgrad(const dg_conv_geom* g, const void* x, const void* dy, float* dw, float* db, void* stream) {
+  g_last_wgrad = WGK_NONE;
   if (!g || !x || !dy || !dw) return DG_ERR_BAD_ARG;
   if (g->dtype != DG_F32 && g->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
   if (g->N <= 0 || g->H <= 0 || g->W <= 0 || (g->stride != 1 && g->stride != 2)) return DG_ERR_BAD_SHAPE;
@@ -1291,6 +1305,7 @@ extern "C" int dg_conv3x3_wgrad(const dg_conv_geom* g, const void* x, const void
 // workgroup.  bf16, stride 1, 128 channels per conv, rows of a multiple of 32 pixels.
 extern "C" int dg_conv3x3_wgrad_dense(const dg_conv_geom* g, int nconv, const void* x, const void* dy, float* const* dw,
                                       float* const* db, void* stream) {
+  g_last_wgrad = WGK_NONE;
   if (!g || !x || !dy || !dw) return DG_ERR_BAD_ARG;
   if (g->dtype != DG_BF16) return DG_ERR_BAD_DTYPE;
   if (nconv < 1 || nconv > 8 || g->N <= 0 || g->H <= 0 || g->W <= 0 || g->stride != 1 || g->pixel_shuffle || g->W % 32) return DG_ERR_BAD_SHAPE;

@@ -50,7 +50,8 @@ typedef enum dg_status {
  * r1/r2/mask are tensors of the OUTPUT's shape in `dtype`.
  * mask_c0 / mask_last (both 0 = the order above, every channel): the mask applies to channels c >= mask_c0 only
  * (multiple of 16), and with mask_last != 0 it multiplies AFTER the accumulate -- the data gradient of a dense block's
- * conv k completes channel slice k-1 of the block's gradient slab and applies that slice's LeakyReLU' in the same pass. */
+ * conv k completes channel slice k-1 of the block's gradient slab and applies that slice's LeakyReLU' in the same pass.
+ * mask_c0 != 0 is refused (DG_ERR_BAD_SHAPE) for a pixel-shuffled destination, whose channels are not the GEMM's columns. */
 typedef struct dg_epilogue {
   const float* bias;
   int has_act;
@@ -191,6 +192,12 @@ int dg_gather_gemm(const dg_gg_desc* d, const dg_epilogue* ep, const void* x, co
  * gather-GEMM, 2 fast path, 8 halo-patch kernel, 16 im2col small-Cin kernel, 32 fp8 halo kernel, 64 streaming stride-2
  * data-gradient kernel). Diagnostic. */
 int dg_last_conv_kernels(void);
+
+/* Which launcher served the calling thread's last dg_conv3x3_wgrad / _wgrad_dense / _wgrad_f8 / _wgrad_dense_f8 call: 0 none (the
+ * call returned before a launch), 1 per-tap kernel, 2 im2col kernel (<= 2 real input channels), 3 narrow row-of-taps kernel,
+ * 4 wide row-of-taps kernel at stride 1, 5 wide kernel at stride 2, 6 dense-block launch of the wide kernel, 7 fp8 kernel.
+ * Reset at the entry of each of those calls.  Diagnostic. */
+int dg_last_wgrad_kernel(void);
 
 /* Host-only planner (no GPU needed): lowers a layer to its gather-GEMM descriptor(s).
  * kind 0 = forward (1 desc), kind 1 = dgrad (1 desc for stride 1, 4 parity classes for stride 2).

@@ -131,6 +131,8 @@ class EmuOps:
             v = v * s1 + r1[sl].float()
         if r2 is not None:
             v = v * s2 + r2[sl].float()
+        assert not (d.dst_ps and mask_c0), "mask_c0 with a pixel-shuffled destination: refused by the library (dg_epilogue)"
+
         def apply_mask(v):       # channels >= mask_c0 only (include/downgan_hip.h, dg_epilogue)
             f = _lgrad(mask[sl].float(), mask_slope)
             f = torch.where(torch.arange(v.shape[-1]) >= mask_c0, f, torch.ones(()))
