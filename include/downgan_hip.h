@@ -161,8 +161,9 @@ int dg_conv3x3_wgrad_dense(const dg_conv_geom* g, int nconv, const void* x, cons
  * dw[co][tap][ci] (fp32, accumulated into) += sum_p dy[p, co] * x[src(p, tap), ci] with E4M3 operands whose scale does not vary
  * along pixels -- the contraction index -- : x = xq * 2^(ex[ci / 32] - 127), dy = dyq * 2^(ey[co / 32] - 127), one E8M0 exponent
  * byte per 32-channel block of the whole tensor (device arrays of Cin / 32 and Cout / 32 bytes).  g->ldx / g->ldy are the pixel
- * strides of xq / dyq in bytes (= elements); g->dtype = DG_BF16 (the precision the fp8 forms stand for).  Stride 1, Cin and Cout
- * multiples of 128, W a multiple of 64, no pixel shuffle; anything else returns DG_ERR_BAD_SHAPE (callers keep the bf16 kernel). */
+ * strides of xq / dyq in bytes (= elements, multiples of 16); g->dtype = DG_BF16 (the precision the fp8 forms stand for).  Stride 1
+ * or 2, Cin and Cout multiples of 128, OUTPUT rows (W / stride) a multiple of 64 pixels, no pixel shuffle; anything else returns
+ * DG_ERR_BAD_SHAPE (callers keep the bf16 kernel). */
 int dg_conv3x3_wgrad_f8(const dg_conv_geom* g, const void* xq, const void* ex, const void* dyq, const void* ey, float* dw,
                         void* stream);
 

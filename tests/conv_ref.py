@@ -31,6 +31,9 @@ against a restatement of the dispatch rules evaluated on the planner's own descr
 library's probes (dg_last_conv_kernels, dg_conv3x3_dgrad_launches, dg_conv3x3_dgrad_stream_eligible, dg_last_wgrad_kernel) -- an
 edit of a shape or of the dispatch cannot quietly turn a case into a second test of another kernel.  Destinations sit inside
 buffers with ``GUARD`` sentinel elements in front and behind; "slab" cases read and write channel slices of wider tensors.
+
+The MXFP8 kernels (csrc/conv_halo_f8.hip, the fp8 kernel of csrc/wgrad.hip; the "f8" entries of ``PATH_BITS`` / ``WGRAD_CODE``) have
+their own operands and table in tests/conv_f8_ref.py, which reuses the references, epilogues, destinations and comparator of this file.
 """
 from __future__ import annotations
 
@@ -267,8 +270,8 @@ def dev(ops, t):
 # name -> the dg_last_conv_kernels() mask a launch on that path leaves (include/downgan_hip.h)
 PATH_BITS = {"rows_generic": 1, "rows_fast": 2, "halo": 8, "halo_ps_src": 8, "halo_s2_4w": 8, "halo_s2_8w": 8, "halo16": 8,
              "seg_interleaved": 8, "seg_per_image": 8, "stream": 64, "im2col_linear": 16, "im2col_tiled": 16,
-             "per_class_generic": 1, "per_class_halo16_fast": 8 | 2}
-WGRAD_CODE = {"tap": 1, "im2col": 2, "rows": 3, "wide_s1": 4, "wide_s2": 5, "dense": 6}
+             "per_class_generic": 1, "per_class_halo16_fast": 8 | 2, "f8": 32}      # "f8": the MXFP8 halo kernel, tests/conv_f8_ref.py
+WGRAD_CODE = {"tap": 1, "im2col": 2, "rows": 3, "wide_s1": 4, "wide_s2": 5, "dense": 6, "f8": 7}
 
 
 def plan(cv, dtype, kind, ldx, ldy):
@@ -384,15 +387,15 @@ def case_epilogues(case, dtype):
     return ok
 
 
-def build_epilogue(name, oshape, nout, dtype, gen, ps=False):
+def build_epilogue(name, oshape, nout, dtype, gen, ps=False, mag=MAG_ADD):
     """(keyword arguments with host tensors, mask_sign or None).  Scalars are 0.25 / 0.5 exactly.  ``ps``: a pixel-shuffled
-    destination, for which the library refuses mask_c0 != 0 (dg_epilogue)."""
+    destination, for which the library refuses mask_c0 != 0 (dg_epilogue).  ``mag``: magnitude of the integer addends."""
     kw, sign = {}, None
     if name == "bias_act":
-        kw = dict(bias=ints((nout,), MAG_ADD, gen, torch.float32), act=0.25)
+        kw = dict(bias=ints((nout,), mag, gen, torch.float32), act=0.25)
     elif name == "bias_r1_r2":
-        kw = dict(bias=ints((nout,), MAG_ADD, gen, torch.float32), r1=ints(oshape, MAG_ADD, gen, dtype), s1=0.5,
-                  r2=ints(oshape, MAG_ADD, gen, dtype), s2=0.5)
+        kw = dict(bias=ints((nout,), mag, gen, torch.float32), r1=ints(oshape, mag, gen, dtype), s1=0.5,
+                  r2=ints(oshape, mag, gen, dtype), s2=0.5)
     elif name == "mask":
         kw = dict(mask=ints(oshape, 2, gen, dtype), mask_slope=0.25)
     elif name == "accumulate":
@@ -403,7 +406,7 @@ def build_epilogue(name, oshape, nout, dtype, gen, ps=False):
         sign = ints(oshape, 2, gen, torch.float32) > 0
         kw = dict(mask_bits=pack_bits(sign), mask_slope=0.25)
     elif name == "out_bits":
-        kw = dict(bias=ints((nout,), MAG_ADD, gen, torch.float32), act=0.25,
+        kw = dict(bias=ints((nout,), mag, gen, torch.float32), act=0.25,
                   out_bits=torch.full(tuple(oshape[:-1]) + (oshape[-1] // 64, 4), 0x5a5a, dtype=torch.int16))
     else:
         assert name == "plain", name

@@ -17,11 +17,15 @@ def test_case_is_exact_on_the_oracle(cid, dtype):
 
 
 def test_every_path_of_the_table_has_a_case():
-    """Each dispatch path the tests name is reached by at least one case (its guard asserts that the case really takes it)."""
+    """Each dispatch path the tests name is reached by at least one case (its guard asserts that the case really takes it); the
+    "f8" entries belong to the table of tests/conv_f8_ref.py, which must reach every fp8 path and both fp8 weight-gradient entries."""
+    from tests import conv_f8_ref as F
     seen = set()
     for c in R.CASES:
         seen |= set(c.expect.values()) if isinstance(c.expect, dict) else {c.expect}
-    assert set(R.PATH_BITS) <= seen and set(R.WGRAD_CODE) <= seen and {"dx_narrow", "dx_wide"} <= seen
+    assert "f8" not in seen
+    assert set(R.PATH_BITS) - {"f8"} <= seen and set(R.WGRAD_CODE) - {"f8"} <= seen and {"dx_narrow", "dx_wide"} <= seen
+    assert {c.expect for c in F.CASES} == set(F.F8_PATHS) and {c.kind for c in F.WCASES} == {"wgrad", "dense"}
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
