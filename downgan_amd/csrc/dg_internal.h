@@ -76,6 +76,10 @@ typedef __attribute__((ext_vector_type(4))) unsigned int dg_u32x4_t;
 __device__ __forceinline__ void dg_fp8_saturate_whole_kernel() { asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1\n\ts_nop 1" ::: "memory"); }
 #define DG_FP8_SAT_ON(dep0, dep1) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1\n\ts_nop 1" : "+v"(dep0), "+v"(dep1))
 #define DG_FP8_SAT_OFF(res0, res1) asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0\n\ts_nop 1" : "+v"(res0), "+v"(res1))
+// `inv` must be a NORMAL fp32 power of two and v * inv must stay inside fp32's range: a product that overflows reaches the converter
+// as Inf and comes out as NaN (0x7F), not as +-448.  dg_quant_mxfp8 meets both by construction (its exponent comes from the block's own
+// maximum: |quotient| < 512, exponent byte <= 247); dg_quant_uniform, whose exponent is the caller's, scales with v_ldexp_f32 and
+// clamps first (csrc/quant.hip pack_fp8x16_any_exp).
 __device__ __forceinline__ dg_u32x4_t pack_fp8x16(const float* v, float inv) {     // (between DG_FP8_SAT_ON and DG_FP8_SAT_OFF)
   dg_u32x4_t o;
 #pragma unroll
@@ -92,11 +96,14 @@ __device__ __forceinline__ dg_u32x4_t pack_fp8x16(const float* v, float inv) {  
 // magnitude bit patterns (equal to the bits of the float maximum for finite values; any NaN / Inf pattern is >= 0x7f800000).
 // The same 16 values straight from their PACKED bf16 form (the words a conv epilogue has just stored: p0 = values 0-7, p1 = 8-15):
 // v_cvt_scalef32_pk_fp8_bf16 divides two bf16 by 2^(E - 127), E = the exponent field of `scale` (mantissa ignored, field 0 = 2^-127),
-// and converts -- no unpacking to fp32, no multiply: one VALU slot per two values instead of four.  Under MODE.FP16_OVFL it equals
-// pack_fp8x16 of the unpacked values with factor 2^(127 - E) for every finite bf16 pattern whose quotient is representable in fp32
-// (tools/fp8_cvt_probe4.hip: all 65536 patterns x six exponents), saturates where that product would have overflowed to Inf (as the
-// emulation's clamp does), and turns +-Inf into +-448 -- blocks holding an Inf or a NaN are poisoned by the caller anyway.  Byte order
-// and word select as v_cvt_pk_fp8_f32 (tools/fp8_cvt_probe5.hip).
+// and converts -- no unpacking to fp32, no multiply: one VALU slot per two values instead of four.  Under MODE.FP16_OVFL it is the
+// OCP E4M3 byte of the exact quotient -- round to nearest even, +-448 beyond -- for EVERY finite bf16 pattern, subnormal ones with
+// their value, under EVERY exponent field 0 .. 254 of `scale` (tests/test_fp8_quant_exact_gpu.py against the integer reference of
+// tests/fp8_quant_ref.py: all 65536 patterns x all 255 fields, test_every_scale_byte_on_every_bf16_pattern).  A zero scale operand (field 0) divides by 2^-127
+// like any other; there is no intermediate fp32 product, so a quotient of any size saturates at +-448 (0x7E / 0xFE), never 0x7F,
+// and field 254 does not lose the values a factor 2^-127 would flush.  What the instruction makes of an Inf or NaN input is not
+// relied on: a block that holds one is poisoned by the caller (mx_poison), and the tests see only that.  Byte order and word select
+// as v_cvt_pk_fp8_f32 (tools/fp8_cvt_probe5.hip; tools/fp8_cvt_probe4.hip compares the two converters at six exponents).
 __device__ __forceinline__ dg_u32x4_t pack_fp8x16_from_bf16(const dg_u32x4_t& p0, const dg_u32x4_t& p1, float scale) {
   typedef __attribute__((ext_vector_type(2))) __bf16 dg_bf16x2_t;
   typedef __attribute__((ext_vector_type(2))) short dg_s16x2_t;

@@ -178,6 +178,20 @@ extern "C" int dg_exp_from_amax(void* amax, int nblocks, int margin, void* out, 
 // ---- stand-alone uniform-scale quantiser (the conv epilogues write this form themselves, dg_epilogue.out_u; this is for the one
 // adjoint that does not come out of a conv: the FC's input gradient): q[r][c] = E4M3(src[r][c] / 2^(exps[c / 32] - 127)), a block
 // that holds a NaN / Inf poisoned like the MXFP8 copy.  One thread = one 32-channel block of one row.
+// The exponent here is the CALLER's, not one derived from the block: any byte 0 .. 254 against any finite value.  The one fp32 multiply
+// of pack_fp8x16 does not cover that: 2^(127 - 254) is no normal fp32 number (mx_inv_scale(254) is the bit pattern of 0.0f: zeros were
+// written), and a product past fp32's range (exponent field of v >= e + 128: |v| >= 4 under the byte 1 an all-zero block gets at
+// margin 1) is Inf, which the converter keeps as NaN under FP16_OVFL -- 0x7F for a finite value, in a block that is not poisoned.
+// v_ldexp_f32 scales exactly over the whole range and the clamp turns the Inf of an overflow into +-448, as the fused copy
+// (pack_fp8x16_from_bf16) and the emulation's clamp do; a NaN / Inf SOURCE poisons its block afterwards (mx_poison).  Two VALU
+// operations per value more than the multiply: this kernel is off the hot path (the FC's input gradient, one adjoint slice per RRDB).
+__device__ __forceinline__ dg_u32x4_t pack_fp8x16_any_exp(const float* v, int e) {
+  float t[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) t[k] = __builtin_amdgcn_fmed3f(__builtin_ldexpf(v[k], 127 - e), -448.f, 448.f);
+  return pack_fp8x16(t, 1.f);
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) quant_uniform_kernel(const T* __restrict__ src, long long rows, long long ld, int C,
                                                             const unsigned char* __restrict__ exps, unsigned char* __restrict__ q, long long ldq) {
@@ -192,9 +206,9 @@ __global__ void __launch_bounds__(256) quant_uniform_kernel(const T* __restrict_
     QLoad<T>::run(src + r * ld + b * 32 + 16, v + 16);
     const unsigned a0 = mx_amax_bits16(v), a1 = mx_amax_bits16(v + 16);
     const unsigned ab = a0 > a1 ? a0 : a1;
-    const float inv = mx_inv_scale((int)exps[b]);
-    *reinterpret_cast<q_u32x4_t*>(q + r * ldq + b * 32) = mx_poison(pack_fp8x16(v, inv), ab);
-    *reinterpret_cast<q_u32x4_t*>(q + r * ldq + b * 32 + 16) = mx_poison(pack_fp8x16(v + 16, inv), ab);
+    const int e = (int)exps[b];
+    *reinterpret_cast<q_u32x4_t*>(q + r * ldq + b * 32) = mx_poison(pack_fp8x16_any_exp(v, e), ab);
+    *reinterpret_cast<q_u32x4_t*>(q + r * ldq + b * 32 + 16) = mx_poison(pack_fp8x16_any_exp(v + 16, e), ab);
   }
 }
 

@@ -375,6 +375,9 @@ int dg_gather_samples(int dtype, const void* src, int64_t HW, int c_real, const 
  * dg_quant_mxfp8: rows x C values (C % 128 == 0, row stride `ld` elements, dtype DG_BF16 or DG_F32) -> OCP FP8 E4M3 bytes
  *   q[rows][ldq] + one E8M0 scale byte per block of 32 consecutive channels (OCP MX layout), scales[rows][C/32];
  *   scale = 2^(floor(log2 amax) - 8), elements = round-to-nearest-even(x / scale) saturated at +-448.
+ *   The scale byte is max(0, exponent field of the block's largest magnitude - 8); fp32 / bf16 subnormal inputs keep their value.
+ *   A block that holds a NaN or an Inf becomes 32 x 0x7F (E4M3 NaN) and gets scale byte 247 (exponent field 255 - 8) -- from
+ *   this kernel, from dg_epilogue.out_q / out_qs and in the emulation alike (tests/test_fp8_quant_exact_*.py).
  *   Serves activations / adjoints (rows = pixels) and conv weight packs (rows = Nout * 9, C = Cred).
  * dg_conv3x3_fwd_f8 / dg_conv3x3_dgrad_f8: dg_conv3x3_fwd / _dgrad with both MFMA operands in that format and fp32
  *   accumulation; `g` describes the layer as for the bf16 calls (g->dtype = DG_BF16: the type of y / dx and of every
@@ -416,7 +419,9 @@ int dg_block_exp_max_batch(const dg_exp_batch* b, int margin, void* scratch, voi
 
 /* Stand-alone form of dg_epilogue.out_u: q[r][c] = E4M3(src[r][c] / 2^(exps[c / 32] - 127)) (saturated at +-448; a block holding a
  * NaN / Inf becomes 32 x NaN), for tensors that do not come out of a conv epilogue (the critic's last adjoint, written by the FC's
- * input gradient).  src bf16 / fp32 [rows][ld], C % 128 == 0, q [rows][ldq] bytes. */
+ * input gradient).  src bf16 / fp32 [rows][ld], C % 128 == 0, q [rows][ldq] bytes.  Every exponent byte 0 .. 254 (2^-127 .. 2^127,
+ * everything dg_block_exp_max / dg_exp_from_amax can return) is served against every finite value, here and in out_u: a quotient
+ * past +-448 saturates however large it is, one below 2^-10 becomes zero. */
 int dg_quant_uniform(int src_dtype, const void* src, int64_t rows, int64_t ld, int C, const void* exps, void* q, int64_t ldq, void* stream);
 
 int dg_quant_mxfp8(int src_dtype, const void* src, int64_t rows, int64_t ld, int C, void* q, int64_t ldq, void* scales,
