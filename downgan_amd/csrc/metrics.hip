@@ -191,7 +191,8 @@ __global__ void msssim_finish_kernel(const float* sums, int levels, int planes, 
     float v = 1.f;
     for (int l = 0; l < levels; ++l) {
       const float* s = sums + ((long long)l * planes + pl) * 2;
-      const float term = fmaxf((l == levels - 1 ? s[0] : s[1]) * cmb.inv_count[l], 0.f);   // ssim at the last scale, cs before
+      const float mean = (l == levels - 1 ? s[0] : s[1]) * cmb.inv_count[l];   // ssim at the last scale, cs before
+      const float term = mean < 0.f ? 0.f : mean;      // relu that keeps a NaN (torch.relu does; fmaxf would turn it into 0)
       v *= powf(term, cmb.weight[l]);
     }
     acc += v;

@@ -339,7 +339,11 @@ typedef struct dg_msssim_combine {
   float weight[DG_SSIM_MAX_LEVELS];     /* 0.0448, 0.2856, 0.3001, 0.2363, 0.1333 */
 } dg_msssim_combine;
 /* per-channel min / max over `pixels` ld-strided pixels (first C channels): partial[DG_MINMAX_PARTS][C][2]
- * (losses.py:15-18, 23-26: x[:, c].min() / .max() over the whole batch) */
+ * (losses.py:15-18, 23-26: x[:, c].min() / .max() over the whole batch).  NaN rule: a NaN pixel is skipped (fminf / fmaxf), so
+ * the result is the min / max of the numbers; a channel with no number at all gives (+inf, -inf).  The NaN still reaches the
+ * metric: dg_normalise_planar keeps it in its pixel, every window that covers it sums to NaN and dg_msssim_finish keeps a NaN
+ * mean, so MS-SSIM of a batch with a NaN is NaN, as the reference's is.  A zero extreme may come back with either sign.
+ * Channels >= C are never read. */
 int dg_minmax_partial(int dtype, const void* x, int64_t pixels, int64_t ld, int C, float* partial, void* stream);
 /* minmax[C][2] = {min, max} over the partials */
 int dg_minmax_finish(const float* partial, int C, float* minmax, void* stream);
@@ -350,14 +354,18 @@ int dg_normalise_planar(int dtype, const void* x, int N, int H, int W, int64_t l
  * the 'valid' (H-win+1)x(W-win+1) window positions of every HxW plane of X, Y (planar fp32) */
 int dg_ssim_level(const float* X, const float* Y, int planes, int H, int W, const dg_ssim_params* p, float* sums,
                   void* stream);
-/* avg_pool2d(kernel 2, stride 2, padding = size % 2 per dim, padded zeros counted) between scales (`ms_ssim`) */
+/* avg_pool2d(kernel 2, stride 2, padding = size % 2 per dim, padded zeros counted) between scales (`ms_ssim`): output (ho, wo)
+ * averages rows 2 ho - H % 2 + {0, 1} and columns 2 wo - W % 2 + {0, 1}, so only the pad row / column on the TOP / LEFT is ever
+ * inside a window; out is [planes][H / 2 + H % 2][W / 2 + W % 2].  H, W >= 2. */
 int dg_avgpool2(const float* in, float* out, int planes, int H, int W, void* stream);
 /* out[0] = sum over planes of prod_l relu(mean_l)^weight_l, mean_l = CS mean for l < levels-1, SSIM mean at the last
- * scale; sums is [levels][planes][2].  The caller divides by the (global) plane count (`size_average=True`). */
+ * scale; sums is [levels][planes][2].  The caller divides by the (global) plane count (`size_average=True`).  relu is
+ * torch.relu's: a negative mean gives 0, a NaN mean stays NaN (and makes out[0] NaN). */
 int dg_msssim_finish(const float* sums, int levels, int planes, const dg_msssim_combine* cmb, float* out, void* stream);
 
 /* Finite-difference physics metrics `divergence_loss` / `vorticity_loss` (DoWnGAN/GAN/losses.py:119-193; known answers in
- * DoWnGAN/GAN/tests/test_losses.py:75-116).  sums[10] (double, pre-zeroed) += {sum r, sum r^2, sum f, sum f^2, sum r*f} of
+ * DoWnGAN/GAN/tests/test_losses.py:75-116).  sums[10] (double) += {sum r, sum r^2, sum f, sum f^2, sum r*f} (the call ADDS to what
+ * sums holds: zero it before the first call of a batch; column 0 of channel 0, row 0 of channel 1 and channels >= 2 are never read) of
  * the divergence (dudy + dvdx) of `hr` (r) and `fake` (f), then the same five of the vorticity (dvdx - dudy); channel 0 = u,
  * channel 1 = v, differences on the [1:, 1:] window.  The host forms MSE(r/std(r), f/std(f)) with the unbiased std. */
 int dg_div_vort_sums(int dtype, const void* hr, int64_t ldhr, const void* fake, int64_t ldfake, int N, int H, int W,
@@ -430,7 +438,8 @@ int dg_conv3x3_fwd_f8(const dg_conv_geom* g, const dg_epilogue* ep, const dg_f8_
 int dg_conv3x3_dgrad_f8(const dg_conv_geom* g, const dg_epilogue* ep, const dg_f8_operands* q, void* dx, void* stream);
 
 /* Dataset preprocessing of the data feed.
- * dg_moments: acc[3] (double, pre-zeroed) += { sum, sum of squares, count } over the non-NaN elements of x[n] -- the
+ * dg_moments: acc[3] (double) += { sum, sum of squares, count } over the non-NaN elements of x[n] (the call ADDS to what acc holds,
+ *   so a record is accumulated chunk by chunk from a zeroed acc; an Inf is an element like any other: counted, sums Inf) -- the
  *   moments behind `xr_standardize_array` (DoWnGAN/helpers/gen_experiment_datasets.py:195-201: da.mean(skipna=True),
  *   da.std(skipna=True), population std), accumulated chunk by chunk over a field's whole record.  x 16-byte aligned.
  * dg_stage_fields: dst[p][k] = (plane[k][p] - mean[k]) * inv_std[k] for p < npix, k < c -- the standardisation itself fused

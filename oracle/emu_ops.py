@@ -441,10 +441,12 @@ class EmuOps:
 
     # MS-SSIM pieces: plain torch restatements of the kernel contracts of csrc/metrics.hip
     def minmax(self, x, c_real, partial, minmax):
+        # fminf / fmaxf semantics (include/downgan_hip.h): a NaN pixel is skipped; a channel of NaNs alone gives (+inf, -inf)
         v = x[..., :c_real].float().reshape(-1, c_real)
+        nan = torch.isnan(v)
         mm = minmax.view(c_real, 2)
-        mm[:, 0] = v.amin(0)
-        mm[:, 1] = v.amax(0)
+        mm[:, 0] = torch.where(nan, torch.full_like(v, float("inf")), v).amin(0)
+        mm[:, 1] = torch.where(nan, torch.full_like(v, float("-inf")), v).amax(0)
 
     def normalise_planar(self, x, c_real, minmax, out):
         mm = minmax.view(c_real, 2)
@@ -478,10 +480,21 @@ class EmuOps:
             v = v * term ** combine.weight[l]
         out[0] = v.sum()
 
-    # frequency separation (csrc/freqsep.hip contracts)
+    # frequency separation (csrc/freqsep.hip contracts): fp32 sums, ONE division by 25 at the end
     @staticmethod
-    def _lp(v):
-        return torch.nn.functional.avg_pool2d(torch.nn.functional.pad(v, (2, 2, 2, 2), mode="replicate"), 5, stride=1)
+    def _clamped(L, d):
+        return (torch.arange(L) + d).clamp(0, L - 1)
+
+    @classmethod
+    def _lp(cls, v):
+        """[N, C, H, W] fp32 -> the 25 replicated-border neighbours added in window order (row-major), then / 25."""
+        H, W = v.shape[2], v.shape[3]
+        s = torch.zeros_like(v)
+        for dy in range(-2, 3):
+            rows = v[:, :, cls._clamped(H, dy)]
+            for dx in range(-2, 3):
+                s = s + rows[:, :, :, cls._clamped(W, dx)]
+        return s / 25.0
 
     def lowpass5(self, x, low=None, high=None):
         v = x.float().permute(0, 3, 1, 2)
@@ -491,11 +504,20 @@ class EmuOps:
         if high is not None:
             high.copy_((v - lo).permute(0, 2, 3, 1).to(high.dtype))
 
+    @classmethod
+    def _fold_matrix(cls, L):
+        """A[q, p] = number of offsets d in [-2, 2] with clamp(p + d, 0, L - 1) == q (fold_count of csrc/freqsep.hip)."""
+        A = torch.zeros(L, L)
+        for d in range(-2, 3):
+            A[cls._clamped(L, d), torch.arange(L)] += 1.0
+        return A
+
     def lowpass5_adjoint(self, g, out):
-        v = g.float().permute(0, 3, 1, 2).clone().requires_grad_(False)
-        probe = torch.zeros_like(v, requires_grad=True)
-        (adj,) = torch.autograd.grad(self._lp(probe), probe, grad_outputs=v)
-        out.copy_(adj.permute(0, 2, 3, 1).to(out.dtype))
+        """out[q] = (sum_p w[q, p] g[p]) / 25 with the integer fold weights w = A_H (x) A_W: one division, after the sum."""
+        v = g.float()
+        s = torch.einsum("qp,npwc->nqwc", self._fold_matrix(g.shape[1]), v)
+        s = torch.einsum("rw,nqwc->nqrc", self._fold_matrix(g.shape[2]), s)
+        out.copy_((s / 25.0).to(out.dtype))
 
     def sum_strided(self, inp, n, stride, scale, out):
         out[0] = inp.reshape(-1)[:n * stride:stride].sum() * scale
@@ -525,6 +547,18 @@ class EmuOps:
         v = x.double().flatten()
         v = v[~torch.isnan(v)]
         acc += torch.stack([v.sum(), (v * v).sum(), torch.tensor(float(v.numel()), dtype=torch.float64)])
+
+    def div_vort_sums(self, hr, fake, sums):
+        """dg_div_vort_sums: sums[10] (float64) += {sum r, sum r^2, sum f, sum f^2, sum r f} of the divergence, then of the vorticity;
+        channel 0 differenced along H, channel 1 along W, both on the [1:, 1:] window."""
+        def dv(t):
+            t = t.double()
+            dudy = t[:, 1:, 1:, 0] - t[:, :-1, 1:, 0]
+            dvdx = t[:, 1:, 1:, 1] - t[:, 1:, :-1, 1]
+            return dudy + dvdx, dvdx - dudy
+        (dr, vr), (df, vf) = dv(hr), dv(fake)
+        five = lambda r, f: [r.sum(), (r * r).sum(), f.sum(), (f * f).sum(), (r * f).sum()]
+        sums += torch.stack(five(dr, df) + five(vr, vf))
 
     def stage_fields(self, planes, mean, inv_std, dst):
         for k, t in enumerate(planes):
