@@ -10,10 +10,13 @@ eps are adopted, otherwise ``config.hyperparams`` applies (the arguments may be 
 """
 from __future__ import annotations
 
+import os
+from typing import Callable, NamedTuple, Optional
+
 import torch
 
 from ..config import hyperparams as hp
-from ..engine import TrainEngine
+from ..engine import METRIC_SINKS, TrainEngine
 from .. import backend
 
 
@@ -151,26 +154,11 @@ class WassersteinGAN:
                                   coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None,
                                   distances=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
-        returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  ``spectra``: a (real, fake)
-        pair of ``spectra.RadialSpectrum`` that also receive the spectra of this batch (TrainEngine.metrics_pass);
-        ``distributions``: likewise a pair of ``histograms.ValueHistogram`` (the fields as the engine stores them: bf16 in bf16
-        mode, real as staged and generated as written); ``maps``: one paired ``gridstats.GridStats`` fed (real, generated);
-        ``fss``: one ``fss.FractionsSkill`` fed the same pair; ``joint``: one ``joint.ValueJoint`` fed the same pair;
-        ``coherence``: one ``spectra.CrossSpectrum`` fed the same pair; ``increments``: one ``increments.Increments`` fed the
-        same pair; ``hist_maps``: one paired ``gridhist.GridHist`` fed the same pair (handed to the engine only when given); ``temporal``: one
-        paired ``temporal.Temporal`` fed the same pair as the next times of its series (likewise only when given); ``helmholtz``:
-        one ``spectra.HelmholtzSpectrum`` fed the same pair (likewise only when given); ``objects``: one paired
-        ``objects.Objects`` fed the same pair (likewise only when given); ``distances``: one ``distmap.Distances`` fed the same
-        pair (likewise only when given)."""
-        more = {} if hist_maps is None else {"hist_maps": hist_maps}
-        if temporal is not None:
-            more["temporal"] = temporal
-        if helmholtz is not None:
-            more["helmholtz"] = helmholtz
-        if objects is not None:
-            more["objects"] = objects
-        if distances is not None:
-            more["distances"] = distances
+        returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  The other keywords are the
+        diagnostic sinks of ``TrainEngine.metrics_pass`` (engine.METRIC_SINKS), accumulators that also receive the real and
+        generated fields of this batch; only those given (not None) are handed to the engine."""
+        given = locals()                                      # the arguments by name, before any other local exists
+        sinks = {name: given[name] for name, _ in METRIC_SINKS if given[name] is not None}
         e, n = self._engine, coarse.shape[0]
         if (e is not None and n < e.B and coarse.shape[2] == e.S and not hasattr(coarse, "nhwc")
                 and (e.dist is None or e.world == 1)):
@@ -182,12 +170,10 @@ class WassersteinGAN:
             xc, xf = self._stage
             o.nchw_to_nhwc(coarse.to(device=o.device, dtype=torch.float32).contiguous(), xc[:n])
             o.nchw_to_nhwc(fine.to(device=o.device, dtype=torch.float32).contiguous(), xf[:n])
-            return e.metrics_pass(xc, xf, n_valid=n, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
-                                  coherence=coherence, increments=increments, **more)
-        e = self._eng(coarse, fine)
-        xc, xf = self._to_native(e, coarse, fine)
-        return e.metrics_pass(xc, xf, spectra=spectra, distributions=distributions, maps=maps, fss=fss, joint=joint,
-                              coherence=coherence, increments=increments, **more)
+        else:
+            e, n = self._eng(coarse, fine), None              # the whole batch counts
+            xc, xf = self._to_native(e, coarse, fine)
+        return e.metrics_pass(xc, xf, n_valid=n, **sinks)
 
     # what the reference's epoch loop does beside the two iterations (wasserstein.py:138-179), switchable because it costs one
     # extra G forward + two critic forwards per batch: the per-batch metrics pass on the train set, the same pass over the test
@@ -281,145 +267,77 @@ class WassersteinGAN:
         keys = [k for k in ("MAE", "MSE", "MSSSIM", "Wass") if rows and rows[0].get(k) is not None]
         return {k: sum(r[k] for r in rows) / len(rows) for k in keys}
 
-    def _spectra_pair(self, fine):
-        from ..spectra import RadialSpectrum
-        N, dev = fine.shape[-1], self._engine.ops.device if self._engine is not None else self.G.device
-        return RadialSpectrum(self.G.n_predictands, N, device=dev), RadialSpectrum(self.G.n_predictands, N, device=dev)
+    # ---- the factories of the HOOKS table below the class: (a fine batch [.., H, W], device) -> one part's accumulator(s)
+    def _spec(self, spec, cls, **kw):
+        """``spec``, or the spec class's z-score default for this generator's channels when it is None."""
+        return spec if spec is not None else cls.zscore(self.G.n_predictands, **kw)
 
-    def _dist_pair(self):
+    def _spectra_pair(self, fine, dev):
+        from ..spectra import RadialSpectrum
+        C, N = self.G.n_predictands, fine.shape[-1]
+        return RadialSpectrum(C, N, device=dev), RadialSpectrum(C, N, device=dev)
+
+    def _dist_pair(self, fine, dev):
         from ..histograms import HistSpec, ValueHistogram
-        spec = self.distribution_spec if self.distribution_spec is not None else HistSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
+        spec = self._spec(self.distribution_spec, HistSpec)
         return ValueHistogram(spec, device=dev), ValueHistogram(spec, device=dev)
 
-    def _map_stats(self, fine):
+    def _map_stats(self, fine, dev):
         from ..gridstats import GridSpec, GridStats
-        spec = self.map_spec if self.map_spec is not None else GridSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return GridStats(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+        return GridStats(self._spec(self.map_spec, GridSpec), fine.shape[-2], fine.shape[-1], paired=True, device=dev)
 
-    def _fss_acc(self, fine):
+    def _fss_acc(self, fine, dev):
         from ..fss import FractionsSkill, FssSpec
-        spec = self.fss_spec if self.fss_spec is not None else FssSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return FractionsSkill(spec, fine.shape[-2], fine.shape[-1], device=dev)
+        return FractionsSkill(self._spec(self.fss_spec, FssSpec), fine.shape[-2], fine.shape[-1], device=dev)
 
-    def _joint_acc(self):
+    def _joint_acc(self, fine, dev):
         from ..joint import JointSpec, ValueJoint
-        spec = self.joint_spec if self.joint_spec is not None else JointSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return ValueJoint(spec, device=dev)
+        return ValueJoint(self._spec(self.joint_spec, JointSpec), device=dev)
 
-    def _increment_acc(self):
-        from ..increments import Increments, IncrementSpec
-        spec = self.increment_spec if self.increment_spec is not None else IncrementSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return Increments(spec, device=dev)
-
-    def _quantile_map_acc(self, fine):
-        from ..gridhist import GridHist
-        from ..histograms import HistSpec
-        spec = self.quantile_map_spec if self.quantile_map_spec is not None else HistSpec.zscore(self.G.n_predictands, bins=64, lim=6.0)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return GridHist(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
-
-    def _temporal_acc(self, fine):
-        from ..temporal import Temporal, TemporalSpec
-        spec = self.temporal_spec if self.temporal_spec is not None else TemporalSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return Temporal(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
-
-    def _objects_acc(self, fine):
-        from ..objects import Objects, ObjectSpec
-        spec = self.objects_spec if self.objects_spec is not None else ObjectSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return Objects(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
-
-    def _distances_acc(self, fine):
-        from ..distmap import Distances, DistSpec
-        spec = self.distance_spec if self.distance_spec is not None else DistSpec.zscore(self.G.n_predictands)
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
-        return Distances(spec, fine.shape[-2], fine.shape[-1], device=dev)
-
-    def _coherence_acc(self, fine):
+    def _coherence_acc(self, fine, dev):
         from ..spectra import CrossSpectrum
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
         return CrossSpectrum(self.G.n_predictands, fine.shape[-1], device=dev)
 
-    def _helmholtz_acc(self, fine):
+    def _increment_acc(self, fine, dev):
+        from ..increments import Increments, IncrementSpec
+        return Increments(self._spec(self.increment_spec, IncrementSpec), device=dev)
+
+    def _quantile_map_acc(self, fine, dev):
+        from ..gridhist import GridHist
+        from ..histograms import HistSpec
+        spec = self._spec(self.quantile_map_spec, HistSpec, bins=64, lim=6.0)
+        return GridHist(spec, fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
+    def _temporal_acc(self, fine, dev):
+        from ..temporal import Temporal, TemporalSpec
+        return Temporal(self._spec(self.temporal_spec, TemporalSpec), fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
+    def _helmholtz_acc(self, fine, dev):
         from ..spectra import HelmholtzSpectrum
-        dev = self._engine.ops.device if self._engine is not None else self.G.device
         return HelmholtzSpectrum(fine.shape[-1], pair=self.helmholtz_pair, scale=self.helmholtz_scale,
                                  rows_up=self.helmholtz_rows_up, device=dev)
 
+    def _objects_acc(self, fine, dev):
+        from ..objects import Objects, ObjectSpec
+        return Objects(self._spec(self.objects_spec, ObjectSpec), fine.shape[-2], fine.shape[-1], paired=True, device=dev)
+
+    def _distances_acc(self, fine, dev):
+        from ..distmap import Distances, DistSpec
+        return Distances(self._spec(self.distance_spec, DistSpec), fine.shape[-2], fine.shape[-1], device=dev)
+
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
-        ("train" / "test"; acc: {"spectra" / "distributions": {part: (real, fake)}, "maps": {part: GridStats}, "fss": {part: FractionsSkill}, "joint": {part: ValueJoint}, "coherence": {part: CrossSpectrum}, "increments": {part: Increments}, "quantile_maps": {part: GridHist}, "temporal": {"test": Temporal}, "helmholtz": {part: HelmholtzSpectrum}, "objects": {part: Objects}, "distances": {part: Distances}}), created on first
-        use; {} when none is on."""
+        ("train" / "test"), created on first use in ``acc`` = {summary key: {part: accumulator(s)}}; {} when none is on."""
         kw = {}
-        if self.log_spectra:
-            sp = acc.setdefault("spectra", {})
-            if part not in sp:
-                sp[part] = self._spectra_pair(fine)
-            kw["spectra"] = sp[part]
-        if self.log_distributions:
-            d = acc.setdefault("distributions", {})
-            if part not in d:
-                d[part] = self._dist_pair()
-            kw["distributions"] = d[part]
-        if self.log_maps:
-            m = acc.setdefault("maps", {})
-            if part not in m:
-                m[part] = self._map_stats(fine)
-            kw["maps"] = m[part]
-        if self.log_fss:
-            f = acc.setdefault("fss", {})
-            if part not in f:
-                f[part] = self._fss_acc(fine)
-            kw["fss"] = f[part]
-        if self.log_joint:
-            j = acc.setdefault("joint", {})
-            if part not in j:
-                j[part] = self._joint_acc()
-            kw["joint"] = j[part]
-        if self.log_coherence:
-            c = acc.setdefault("coherence", {})
-            if part not in c:
-                c[part] = self._coherence_acc(fine)
-            kw["coherence"] = c[part]
-        if self.log_increments:
-            i = acc.setdefault("increments", {})
-            if part not in i:
-                i[part] = self._increment_acc()
-            kw["increments"] = i[part]
-        if self.log_quantile_maps:
-            h = acc.setdefault("quantile_maps", {})
-            if part not in h:
-                h[part] = self._quantile_map_acc(fine)
-            kw["hist_maps"] = h[part]
-        if self.log_temporal and part == "test":                 # the test part only: the train batches are shuffled samples
-            t = acc.setdefault("temporal", {})
-            if part not in t:
-                t[part] = self._temporal_acc(fine)
-            kw["temporal"] = t[part]
-        if self.log_helmholtz:
-            z = acc.setdefault("helmholtz", {})
-            if part not in z:
-                z[part] = self._helmholtz_acc(fine)
-            kw["helmholtz"] = z[part]
-        if self.log_objects:
-            b = acc.setdefault("objects", {})
-            if part not in b:
-                b[part] = self._objects_acc(fine)
-            kw["objects"] = b[part]
-        if self.log_distances:
-            d = acc.setdefault("distances", {})
-            if part not in d:
-                d[part] = self._distances_acc(fine)
-            kw["distances"] = d[part]
+        for h in HOOKS:
+            if getattr(self, h.flag) and part in h.parts:
+                accs = acc.setdefault(h.key, {})
+                if part not in accs:
+                    accs[part] = h.make(self, fine, self._engine.ops.device if self._engine is not None else self.G.device)
+                kw[h.sink] = accs[part]
         return kw
 
-    def _helmholtz_summary(self, acc):
+    def _helmholtz_summary(self, hook, part, acc, epoch):
         """The eight mean planes by name ([K] each), "div_frac_real", "div_frac_fake" (div / (rot + div), NaN on ring 0),
         "coh_rot", "coh_div": [K], "k_eff_rot", "k_eff_div" (effective resolution of each part at ``helmholtz_threshold``),
         "wavelength_px_rot", "wavelength_px_div" and "fields" of one part's accumulator, summed over the data-parallel ranks
@@ -436,7 +354,7 @@ class WassersteinGAN:
         out["fields"] = acc.count
         return out
 
-    def _coherence_summary(self, acc):
+    def _coherence_summary(self, hook, part, acc, epoch):
         """{"real", "fake", "co": [C][K] mean spectra of the real and generated fields and their co-spectrum, "coherence",
         "rel_error": [C][K], "k_eff", "wavelength_px": [C] effective resolution at ``coherence_threshold``, "fields": count} of
         one part's accumulator, summed over the data-parallel ranks first."""
@@ -448,73 +366,20 @@ class WassersteinGAN:
                 "rel_error": relative_error_spectrum(s).tolist(), "k_eff": [int(k) for k in k_eff],
                 "wavelength_px": [float(w) for w in wavelength_px(k_eff, acc.N)], "fields": acc.count}
 
-    def _temporal_summary(self, part, acc, epoch):
-        """The JSON-serialisable summary of the test part's accumulator (one rank: there is nothing to reduce); the
-        TemporalResult is kept in ``temporal_results`` and, with ``temporal_dir``, saved."""
-        res = acc.result()
-        self.temporal_results[part] = res
-        if self.temporal_dir is not None:
-            import os
-            res.save(os.path.join(self.temporal_dir, str(epoch), part))
-        return res.summary()
+    def _result_summary(self, h, part, acc, epoch):
+        """The JSON-serialisable summary of one part's accumulator of hook ``h`` (summed over the data-parallel ranks first,
+        where ``h.reduce``); its result is kept in the ``h.results`` attribute and, with the ``h.dir`` attribute set, saved
+        under <dir>/<epoch>/<part> -- by the first rank where the ranks hold the same reduced result.  ``h.q``: the attribute
+        whose quantile levels both ``save`` and ``summary`` take."""
+        res = (acc.reduce_(self.dist) if h.reduce else acc).result()
+        getattr(self, h.results)[part] = res
+        args = () if h.q is None else (tuple(getattr(self, h.q)),)
+        directory = None if h.dir is None else getattr(self, h.dir)
+        if directory is not None and (not h.reduce or self.dist is None or self.dist.rank == 0):
+            res.save(os.path.join(directory, str(epoch), part), *args)
+        return res.summary(*args)
 
-    def _quantile_map_summary(self, part, acc, epoch):
-        """The JSON-serialisable summary of one part's accumulator (the table summed exactly over the data-parallel ranks
-        first); the GridHistMaps is kept in ``quantile_map_results`` and, with ``quantile_map_dir``, saved by the first rank."""
-        res = acc.reduce_(self.dist).result()
-        self.quantile_map_results[part] = res
-        q = tuple(self.quantile_map_q)
-        if self.quantile_map_dir is not None and (self.dist is None or self.dist.rank == 0):
-            import os
-            res.save(os.path.join(self.quantile_map_dir, str(epoch), part), q)
-        return res.summary(q)
-
-    def _increment_summary(self, part, acc):
-        """The JSON-serialisable summary of one part's accumulator (counts summed exactly, moments in fp64, over the data-parallel
-        ranks first); the IncrementResult is kept in ``increment_results``."""
-        res = acc.reduce_(self.dist).result()
-        self.increment_results[part] = res
-        return res.summary()
-
-    def _joint_summary(self, part, acc):
-        """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
-        Joint is kept in ``joint_results``."""
-        res = acc.reduce_(self.dist).result()
-        self.joint_results[part] = res
-        return res.summary()
-
-    def _objects_summary(self, part, acc):
-        """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the
-        ObjectsResult is kept in ``objects_results``."""
-        res = acc.reduce_(self.dist).result()
-        self.objects_results[part] = res
-        return res.summary()
-
-    def _distances_summary(self, part, acc):
-        """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the
-        DistanceResult is kept in ``distance_results``."""
-        res = acc.reduce_(self.dist).result()
-        self.distance_results[part] = res
-        return res.summary()
-
-    def _fss_summary(self, part, acc):
-        """The JSON-serialisable summary of one part's accumulator (summed exactly over the data-parallel ranks first); the
-        FssResult is kept in ``fss_results``."""
-        res = acc.reduce_(self.dist).result()
-        self.fss_results[part] = res
-        return res.summary()
-
-    def _map_summary(self, part, stats, epoch):
-        """The JSON-serialisable summary of one part's accumulator (summed over the data-parallel ranks first); the GridMaps is
-        kept in ``map_results`` and, with ``map_dir``, saved by the first rank."""
-        maps = stats.reduce_(self.dist).result()
-        self.map_results[part] = maps
-        if self.map_dir is not None and (self.dist is None or self.dist.rank == 0):
-            import os
-            maps.save(os.path.join(self.map_dir, str(epoch), part))
-        return maps.summary()
-
-    def _distribution_summary(self, part, pair):
+    def _distribution_summary(self, hook, part, pair, epoch):
         """The JSON-serialisable summary of an accumulator pair (summed over the data-parallel ranks first): channel names,
         field count, quantiles / moments / extrema / out-of-range and NaN counts of the real and the generated values, and per
         channel their W1 and KS distances and the generated values' exceedance of the real tail quantiles."""
@@ -529,7 +394,7 @@ class WassersteinGAN:
                 "fake": side(fake), "w1": wasserstein1(real, fake).tolist(), "ks": ks_distance(real, fake).tolist(),
                 "exceed_fake": exceedance(real, fake, eq).tolist()}
 
-    def _spectra_summary(self, pair):
+    def _spectra_summary(self, hook, part, pair, epoch):
         """{"real", "fake": [C][K] mean spectra, "lsd": [C] log-spectral distance of fake to real, "fields": count} of an
         accumulator pair, summed over the data-parallel ranks first."""
         from ..spectra import log_spectral_distance
@@ -552,7 +417,7 @@ class WassersteinGAN:
             _helm_pair(self.helmholtz_pair, self.G.n_predictands)
             _helm_scale(self.helmholtz_scale, self.helmholtz_rows_up)
         log, train_metrics, test_metrics = [], [], []
-        acc = {}                                              # "spectra" / "distributions" / "maps" / "fss" / "joint" / "coherence" -> {"train" / "test": accumulators}
+        acc = {}                                              # summary key of HOOKS -> {"train" / "test": accumulator(s)}
         for data in dataloader:
             coarse, fine = data[0], data[1]
             gen_step = self.num_steps % hp.critic_iterations == 0                 # :136
@@ -582,45 +447,15 @@ class WassersteinGAN:
                     raise ValueError("the test loader yielded no batch: no test metrics for this epoch (wasserstein.py:157-170)")
                 summary["test"] = self._metric_means(test_metrics)                   # :170
                 summary["test_batches"] = len(test_metrics)
-        if (self.log_spectra or self.log_distributions or self.log_maps or self.log_fss or self.log_joint
-                or self.log_coherence or self.log_increments or self.log_quantile_maps or self.log_temporal or self.log_helmholtz
-                or self.log_objects or self.log_distances):
+        on = [h for h in HOOKS if getattr(self, h.flag)]
+        if on:
             if testdataloader is not None and not self.log_metrics:
                 for data in testdataloader:
                     self.gen_batch_and_log_metrics(data[0], data[1], **self._hooks(acc, "test", data[1]))
-            if self.log_spectra:
-                summary["spectra"] = {k: self._spectra_summary(v) for k, v in acc.get("spectra", {}).items()}
-            if self.log_distributions:
-                self.distribution_results = {}
-                summary["distributions"] = {k: self._distribution_summary(k, v) for k, v in acc.get("distributions", {}).items()}
-            if self.log_maps:
-                self.map_results = {}
-                summary["maps"] = {k: self._map_summary(k, v, epoch) for k, v in acc.get("maps", {}).items()}
-            if self.log_fss:
-                self.fss_results = {}
-                summary["fss"] = {k: self._fss_summary(k, v) for k, v in acc.get("fss", {}).items()}
-            if self.log_joint:
-                self.joint_results = {}
-                summary["joint"] = {k: self._joint_summary(k, v) for k, v in acc.get("joint", {}).items()}
-            if self.log_coherence:
-                summary["coherence"] = {k: self._coherence_summary(v) for k, v in acc.get("coherence", {}).items()}
-            if self.log_increments:
-                self.increment_results = {}
-                summary["increments"] = {k: self._increment_summary(k, v) for k, v in acc.get("increments", {}).items()}
-            if self.log_quantile_maps:
-                self.quantile_map_results = {}
-                summary["quantile_maps"] = {k: self._quantile_map_summary(k, v, epoch) for k, v in acc.get("quantile_maps", {}).items()}
-            if self.log_temporal:
-                self.temporal_results = {}
-                summary["temporal"] = {k: self._temporal_summary(k, v, epoch) for k, v in acc.get("temporal", {}).items()}
-            if self.log_helmholtz:
-                summary["helmholtz"] = {k: self._helmholtz_summary(v) for k, v in acc.get("helmholtz", {}).items()}
-            if self.log_objects:
-                self.objects_results = {}
-                summary["objects"] = {k: self._objects_summary(k, v) for k, v in acc.get("objects", {}).items()}
-            if self.log_distances:
-                self.distance_results = {}
-                summary["distances"] = {k: self._distances_summary(k, v) for k, v in acc.get("distances", {}).items()}
+            for h in on:
+                if h.results is not None:
+                    setattr(self, h.results, {})
+                summary[h.key] = {part: h.summary(self, h, part, a, epoch) for part, a in acc.get(h.key, {}).items()}
         if self.checkpoint_dir is not None:
             from ..checkpoint import log_network_models
             summary["checkpoints"] = log_network_models(self.C, self.G, epoch, self.checkpoint_dir)   # :178
@@ -635,3 +470,39 @@ class WassersteinGAN:
         for epoch in range(hp.epochs if epochs is None else epochs):
             history.append(self._train_epoch(dataloader, testdataloader, epoch))
         return history
+
+
+class Hook(NamedTuple):
+    """One opt-in per-epoch diagnostic of the trainer.  The trainer's attributes are given by name and read when an epoch
+    needs them, so they can be set on the class or on an instance at any time."""
+    key: str                                   # of the epoch summary, and of the epoch's accumulators
+    flag: str                                  # the attribute that switches it on
+    sink: str                                  # the keyword of gen_batch_and_log_metrics / TrainEngine.metrics_pass it feeds
+    make: Callable                             # (trainer, fine batch, device) -> one part's accumulator, or (real, fake) pair
+    summary: Callable = WassersteinGAN._result_summary     # (trainer, hook, part, accumulator, epoch) -> JSON-serialisable dict
+    results: Optional[str] = None              # the attribute that keeps {part: result} of the last logged epoch, if any
+    parts: tuple = ("train", "test")           # the parts of the epoch it is fed in
+    # what _result_summary reads beside ``results``:
+    dir: Optional[str] = None                  # the attribute of the directory the results are saved under (None: never saved)
+    q: Optional[str] = None                    # the attribute of the quantile levels that save() and summary() take
+    reduce: bool = True                        # whether the accumulator is summed over the data-parallel ranks first
+
+
+HOOKS = (                                      # in the order of the epoch summary's keys
+    Hook("spectra", "log_spectra", "spectra", WassersteinGAN._spectra_pair, WassersteinGAN._spectra_summary),
+    Hook("distributions", "log_distributions", "distributions", WassersteinGAN._dist_pair, WassersteinGAN._distribution_summary,
+         results="distribution_results"),
+    Hook("maps", "log_maps", "maps", WassersteinGAN._map_stats, results="map_results", dir="map_dir"),
+    Hook("fss", "log_fss", "fss", WassersteinGAN._fss_acc, results="fss_results"),
+    Hook("joint", "log_joint", "joint", WassersteinGAN._joint_acc, results="joint_results"),
+    Hook("coherence", "log_coherence", "coherence", WassersteinGAN._coherence_acc, WassersteinGAN._coherence_summary),
+    Hook("increments", "log_increments", "increments", WassersteinGAN._increment_acc, results="increment_results"),
+    Hook("quantile_maps", "log_quantile_maps", "hist_maps", WassersteinGAN._quantile_map_acc, results="quantile_map_results",
+         dir="quantile_map_dir", q="quantile_map_q"),
+    # the test part only: the train batches are shuffled samples; one rank (_train_epoch), so there is nothing to reduce
+    Hook("temporal", "log_temporal", "temporal", WassersteinGAN._temporal_acc, results="temporal_results", dir="temporal_dir",
+         reduce=False, parts=("test",)),
+    Hook("helmholtz", "log_helmholtz", "helmholtz", WassersteinGAN._helmholtz_acc, WassersteinGAN._helmholtz_summary),
+    Hook("objects", "log_objects", "objects", WassersteinGAN._objects_acc, results="objects_results"),
+    Hook("distances", "log_distances", "distances", WassersteinGAN._distances_acc, results="distance_results"),
+)

@@ -1007,6 +1007,13 @@ class NativeGenerator:
 
 
 # =============================================================================================== train step
+# The diagnostic sinks of TrainEngine.metrics_pass in the order it feeds them: (keyword, whether the sink is a (real, fake) pair
+# of single-series accumulators, each fed its own side, and not one accumulator fed the pair)
+METRIC_SINKS = (("spectra", True), ("coherence", False), ("helmholtz", False), ("distributions", True), ("maps", False),
+                ("fss", False), ("joint", False), ("increments", False), ("hist_maps", False), ("temporal", False),
+                ("objects", False), ("distances", False))
+
+
 class TrainEngine:
     """One WGAN-GP train step = WassersteinGAN._critic_train_iteration (+ _generator_train_iteration
     every ``critic_iterations`` steps), reference DoWnGAN/GAN/wasserstein.py:27-83,131-147.
@@ -1245,31 +1252,20 @@ class TrainEngine:
         ``n_valid`` < B: only the first n_valid samples of the (padded) batch count -- a smaller test batch evaluated on the
         training engine's buffers instead of re-binding the whole engine to its size; every sample is independent on this path
         (no batch norm), so the padded rows change nothing in the first n_valid.
-        ``spectra``: a ``(real, fake)`` pair of ``spectra.RadialSpectrum`` that receive the spectra of ``fine[:n]`` and of the
-        ``fake[:n]`` this pass generates anyway (no extra generator forward); the returned metrics are the same.
-        ``distributions``: likewise a ``(real, fake)`` pair of ``histograms.ValueHistogram``.  Both read the fields as stored:
-        in bf16 mode the staged real fields and the generated ones are bf16 (spacing 0.031 on [4, 8), coarser than the default
-        bin width of 0.0098), so the histograms are those of the bf16 values.
-        ``maps``: a paired ``gridstats.GridStats`` that receives (fine[:n], fake[:n]) in one call: the per-gridpoint statistics
-        of both series and of their difference.
-        ``fss``: a ``fss.FractionsSkill`` that likewise receives (fine[:n], fake[:n]) in one call: the fractions skill score's
-        exact sums of the pair.
-        ``joint``: a ``joint.ValueJoint`` that likewise receives (fine[:n], fake[:n]) in one call: the wind roses and the
-        real-vs-generated densities of the pair.
-        ``increments``: an ``increments.Increments`` that likewise receives (fine[:n], fake[:n]) in one call: the increment
-        histograms of both series (structure functions, flatness, W1 / KS per separation).
-        ``coherence``: a ``spectra.CrossSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the cross spectra
-        of the pair (per-scale coherence, error spectrum, effective resolution).
-        ``hist_maps``: a paired ``gridhist.GridHist`` that likewise receives (fine[:n], fake[:n]) in one call: the per-gridpoint
-        histograms of both series (local quantiles, W1 / KS per pixel).
-        ``temporal``: a paired ``temporal.Temporal`` that likewise receives (fine[:n], fake[:n]) in one call, as the next n times
-        of its series: the caller feeds the batches in time order.
-        ``helmholtz``: a ``spectra.HelmholtzSpectrum`` that likewise receives (fine[:n], fake[:n]) in one call: the rotational and
-        divergent kinetic energy spectra of both wind fields and the coherence of each part.
-        ``objects``: a paired ``objects.Objects`` that likewise receives (fine[:n], fake[:n]) in one call: the connected exceedance
-        objects of both series, pooled on the host (one synchronising copy of the object count per call).
-        ``distances``: a ``distmap.Distances`` that likewise receives (fine[:n], fake[:n]) in one call: the distance transforms of
-        both masks and the distance measures of the pair, pooled on the host (one synchronising copy of the records per call)."""
+        The other keywords are the diagnostic sinks of METRIC_SINKS, each an accumulator (None: not given) that receives
+        ``fine[:n]`` and the ``fake[:n]`` this pass generates anyway (no extra generator forward) in METRIC_SINKS' order; the
+        returned metrics are the same.  ``spectra`` (``spectra.RadialSpectrum``) and ``distributions``
+        (``histograms.ValueHistogram``) are ``(real, fake)`` pairs of single-series accumulators, one ``add`` each; every
+        other sink is one accumulator that receives (fine[:n], fake[:n]) in one ``add``: ``coherence``
+        (``spectra.CrossSpectrum``), ``helmholtz`` (``spectra.HelmholtzSpectrum``), ``maps`` (paired ``gridstats.GridStats``),
+        ``fss`` (``fss.FractionsSkill``), ``joint`` (``joint.ValueJoint``), ``increments`` (``increments.Increments``),
+        ``hist_maps`` (paired ``gridhist.GridHist``), ``temporal`` (paired ``temporal.Temporal``), ``objects`` (paired
+        ``objects.Objects``), ``distances`` (``distmap.Distances``).
+        The histograms read the fields as stored: in bf16 mode the staged real fields and the generated ones are bf16
+        (spacing 0.031 on [4, 8), coarser than the default bin width of 0.0098), so the histograms are those of the bf16
+        values.  ``temporal`` takes the pair as the next n times of its series: the caller feeds the batches in time order.
+        ``objects`` and ``distances`` pool their records on the host (one synchronising copy per call each)."""
+        given = locals()                                          # the arguments by name, before any other local exists
         o, C, B = self.ops, self.C, self.B
         n = B if n_valid is None else int(n_valid)
         assert 1 <= n <= B
@@ -1278,32 +1274,15 @@ class TrainEngine:
         m.zero_()
         o.l1(fine[:n], fake[:n], m[0:1])
         o.sqdiff(fine[:n], fake[:n], m[1:2])
-        if spectra is not None:
-            spectra[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
-            spectra[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if coherence is not None:
-            coherence.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if helmholtz is not None:
-            helmholtz.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if distributions is not None:
-            distributions[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
-            distributions[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if maps is not None:
-            maps.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if fss is not None:
-            fss.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if joint is not None:
-            joint.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if increments is not None:
-            increments.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if hist_maps is not None:
-            hist_maps.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if temporal is not None:
-            temporal.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if objects is not None:
-            objects.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
-        if distances is not None:
-            distances.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
+        for name, pair in METRIC_SINKS:
+            sink = given[name]
+            if sink is None:
+                continue
+            if pair:
+                sink[0].add(fine, n_valid=n, nhwc=True, channels=self.G.npred)
+                sink[1].add(fake, n_valid=n, nhwc=True, channels=self.G.npred)
+            else:
+                sink.add(fine, fake, n_valid=n, nhwc=True, channels=self.G.npred)
         out = C.forward(fine)
         o.sum_strided(out, n, out.stride(0), 1.0 / n, self._sc("c_real_mean"))
         out = C.forward(fake)
