@@ -28,10 +28,10 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fields
 from .fss import allreduce_ints
 from .gridstats import _jsonable
-from .histograms import C_MAX, _default_ops, _descriptor, _f32, _fields
+from .histograms import C_MAX, _default_ops, _f32
 
 THR_MAX, SIDE_MAX, RINGS_MAX, CUTOFF_MAX, COLS, FAR = (_lib.DIST_MAX_THR, _lib.DIST_MAX_SIDE, _lib.DIST_MAX_RINGS,
                                                        _lib.DIST_MAX_CUTOFF, _lib.DIST_COLS, _lib.DIST_FAR)
@@ -193,36 +193,27 @@ class HostOps:
                 d2[t] = torch.from_numpy(d.reshape(d2.shape[1:]))
 
 
-def _series(spec, x, nhwc, channels, what, grid=None):
-    x, nhwc, Cn, T = _fields(x, channels, nhwc)
-    if Cn != spec.C:
-        raise ValueError(f"the DistSpec describes C = {spec.C} input channels but the {what} fields hold {Cn}")
-    hw = tuple(x.shape[1:3]) if nhwc else tuple(x.shape[2:4])
-    if not (1 <= hw[0] <= SIDE_MAX and 1 <= hw[1] <= SIDE_MAX):
-        raise ValueError(f"distmap needs a grid of 1 <= H, W <= {SIDE_MAX} (got {hw[0]} x {hw[1]})")
-    if grid is not None and hw != grid:
-        raise ValueError(f"Distances was made for a {grid[0]} x {grid[1]} grid but the {what} fields are {hw[0]} x {hw[1]}")
-    return x, nhwc, Cn, T, hw
-
-
 def distance_transform(x, spec=None, nhwc=False, channels=None, ops=None):
     """The exact squared Euclidean distance transform of the exceedance masks of a series of fields, on the GPU -> int32 tensor
     [T, nout, K, H, W]: d2 = the squared distance in pixels to the nearest pixel with y > thr[j][k] (0 on the mask; FAR = 2^30
     everywhere where a field has none).  spec None: ``DistSpec.zscore`` of the fields' channels; layouts as ``Distances.add``."""
+    x, x_nhwc, Cn, T, H, W = sx = fields.series(x, channels, nhwc, "distmap")
     if spec is None:
-        spec = DistSpec.zscore(_fields(x, channels, nhwc)[2])
+        spec = DistSpec.zscore(Cn)
     if not isinstance(spec, DistSpec):
         raise TypeError(f"distance_transform takes a DistSpec (got {type(spec).__name__})")
-    x, x_nhwc, Cn, T, (H, W) = _series(spec, x, nhwc, channels, "given")
+    fields.agree(sx, spec, "given")
+    if not (1 <= H <= SIDE_MAX and 1 <= W <= SIDE_MAX):
+        raise ValueError(f"distmap needs a grid of 1 <= H, W <= {SIDE_MAX} (got {H} x {W})")
     o = ops if ops is not None else _default_ops(x.device)
     s = spec.struct()
-    _, f1 = _descriptor(o, x[:1], x_nhwc, Cn)
+    _, f1 = fields.descriptor(o, x[:1], x_nhwc, Cn)
     per_field = max(1, o.distmap_ws_bytes(f1, H, W, s)) + 8 * spec.nout * spec.K * H * W
     tc = max(1, min(T, WS_CAP // per_field))
     out = torch.empty(T, spec.nout, spec.K, H, W, dtype=torch.int32, device=o.device)
     for t0 in range(0, T, tc):
         m = min(tc, T - t0)
-        kx, fx = _descriptor(o, x[t0:t0 + m], x_nhwc, Cn)
+        kx, fx = fields.descriptor(o, x[t0:t0 + m], x_nhwc, Cn)
         d2 = torch.empty(m, 2, spec.nout, spec.K, H * W, dtype=torch.int32, device=o.device)   # the side-1 planes stay unwritten
         o.distmap(fx, None, H, W, s, d2=d2)
         out[t0:t0 + m] = d2[:, 0].view(m, spec.nout, spec.K, H, W)
@@ -409,28 +400,19 @@ class Distances:
         with ``nhwc`` a [T, H, W, c_pad] store of which the leading ``channels`` are read; a ``NativeBatch``); the two series may
         differ in layout and dtype: pass ``nhwc`` as a pair (real, fake) then.  Every dg_distmap call ends with one
         synchronising copy of its records."""
-        fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-        if len(fl) != 2:
-            raise ValueError(f"nhwc is one flag or a (real, fake) pair (got {nhwc!r})")
-        a, a_nhwc, Cn, T, _ = _series(self.spec, real, fl[0], channels, "real", (self.H, self.W))
-        b, b_nhwc, _, Tb, _ = _series(self.spec, fake, fl[1], channels, "generated", (self.H, self.W))
-        if Tb != T:
-            raise ValueError(f"real and generated batches differ in length ({T} and {Tb})")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "distmap", self.spec, "Distances", (self.H, self.W))
         if self._struct is None:
             self._struct = self.spec.struct()
         o, sp = self.ops, self.spec
         if self._rings is None:
             self._rings = torch.zeros(sp.nout, sp.K, 2, sp.nring + 2, dtype=torch.int64, device=o.device)
-        _, f1 = _descriptor(o, a[:1], a_nhwc, Cn)
+        _, f1 = fields.descriptor(o, a.x[:1], a.nhwc, a.C)
         per_field = max(1, o.distmap_ws_bytes(f1, self.H, self.W, self._struct))
         tc = max(1, min(n, self.ws_cap // per_field))
         for t0 in range(0, n, tc):
             m = min(tc, n - t0)
-            ka, fa = _descriptor(o, a[t0:t0 + m], a_nhwc, Cn)
-            kb, fb = _descriptor(o, b[t0:t0 + m], b_nhwc, Cn)
+            ka, fa = fields.descriptor(o, a.x[t0:t0 + m], a.nhwc, a.C)
+            kb, fb = fields.descriptor(o, b.x[t0:t0 + m], b.nhwc, b.C)
             records = torch.empty(m, sp.nout, sp.K, COLS, dtype=torch.int64, device=o.device)
             o.distmap(fa, fb, self.H, self.W, self._struct, records=records, rings=self._rings)
             self.calls += 1
@@ -481,12 +463,10 @@ class Distances:
 def distances(real, fake, spec=None, n_valid=None, nhwc=False, channels=None, ops=None, keep_records=False):
     """Distance measures of a (real, generated) pair of series, on the GPU -> ``DistanceResult``.  spec None:
     ``DistSpec.zscore`` of the fields' channels; the other arguments as ``Distances.add``."""
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    x, x_nhwc, Cn, _ = _fields(real, channels, fl[0])
+    Cn, H, W, device = fields.one_shot(real, nhwc, channels, "distmap")
     if spec is None:
         spec = DistSpec.zscore(Cn)
     if not isinstance(spec, DistSpec):
         raise TypeError(f"distances takes a DistSpec (got {type(spec).__name__})")
-    H, W = (x.shape[1:3] if x_nhwc else x.shape[2:4])
-    acc = Distances(spec, H, W, device=x.device, ops=ops, keep_records=keep_records)
+    acc = Distances(spec, H, W, device=device, ops=ops, keep_records=keep_records)
     return acc.add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

@@ -23,9 +23,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fields
 from .gridstats import _jsonable
-from .histograms import C_MAX, _default_ops, _descriptor, _f32, _fields
+from .histograms import C_MAX, _default_ops, _f32
 
 THR_MAX, SCALES_MAX, SIDE_MAX = _lib.FSS_MAX_THR, _lib.FSS_MAX_SCALES, _lib.FSS_MAX_SIDE
 WS_CAP = 512 << 20           # bytes of dg_fss workspace at most: a batch is cut into chunks of fields (at least one)
@@ -258,15 +258,6 @@ class FractionsSkill:
             self._ops = _default_ops(self.device)
         return self._ops
 
-    def _series(self, x, nhwc, channels, what):
-        x, nhwc, Cn, T = _fields(x, channels, nhwc)
-        if Cn != self.spec.C:
-            raise ValueError(f"the FssSpec describes C = {self.spec.C} input channels but the {what} fields hold {Cn}")
-        hw = tuple(x.shape[1:3]) if nhwc else tuple(x.shape[2:4])
-        if hw != (self.H, self.W):
-            raise ValueError(f"FractionsSkill was made for a {self.H} x {self.W} grid but the {what} fields are {hw[0]} x {hw[1]}")
-        return x, nhwc, Cn, T
-
     def _drain(self):
         """Move the device accumulators into the host totals (one synchronising copy) and zero them."""
         for host, dev in ((self._sums, self._dev_sums), (self._rates, self._dev_rates)):
@@ -280,29 +271,20 @@ class FractionsSkill:
         """Add the first ``n_valid`` (default: all) field pairs of a batch.  Layouts as ``histograms.histogram`` ([T, C, H, W];
         with ``nhwc`` a [T, H, W, c_pad] store of which the leading ``channels`` are read; a ``NativeBatch``); the two series
         may differ in layout and dtype: pass ``nhwc`` as a pair (real, fake) then."""
-        fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-        if len(fl) != 2:
-            raise ValueError(f"nhwc is one flag or a (real, fake) pair (got {nhwc!r})")
-        a, a_nhwc, Cn, T = self._series(real, fl[0], channels, "real")
-        b, b_nhwc, _, Tb = self._series(fake, fl[1], channels, "generated")
-        if Tb != T:
-            raise ValueError(f"real and generated batches differ in length ({T} and {Tb})")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "fss", self.spec, "FractionsSkill", (self.H, self.W))
         if self._struct is None:
             self._struct = self.spec.struct()
         o, mb = self.ops, self._max_bound
         limit = min(DRAIN_LIMIT, CALL_LIMIT)
-        _, f1 = _descriptor(o, a[:1], a_nhwc, Cn)
+        _, f1 = fields.descriptor(o, a.x[:1], a.nhwc, a.C)
         per_field = max(1, o.fss_ws_bytes(f1, self.H, self.W, self._struct))
         tc = max(1, min(n, WS_CAP // per_field, limit // mb))         # fields per call: workspace cap and per-call headroom
         for t0 in range(0, n, tc):
             m = min(tc, n - t0)
             if self._dev_bound and self._dev_bound + m * mb > limit:
                 self._drain()
-            ka, fa = _descriptor(o, a[t0:t0 + m], a_nhwc, Cn)
-            kb, fb = _descriptor(o, b[t0:t0 + m], b_nhwc, Cn)
+            ka, fa = fields.descriptor(o, a.x[t0:t0 + m], a.nhwc, a.C)
+            kb, fb = fields.descriptor(o, b.x[t0:t0 + m], b.nhwc, b.C)
             o.fss(fa, fb, self.H, self.W, self._struct, self._dev_sums, self._dev_rates)
             self._dev_bound += m * mb
         self.fields += n
@@ -328,12 +310,10 @@ class FractionsSkill:
 def fss(real, fake, spec=None, n_valid=None, nhwc=False, channels=None, ops=None):
     """Fractions skill score of a (real, generated) pair of series of fields on the GPU -> ``FssResult``.  spec None:
     ``FssSpec.zscore`` of the fields' channels; the other arguments as ``FractionsSkill.add``."""
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    x, x_nhwc, Cn, _ = _fields(real, channels, fl[0])
+    Cn, H, W, device = fields.one_shot(real, nhwc, channels, "fss")
     if spec is None:
         spec = FssSpec.zscore(Cn)
     if not isinstance(spec, FssSpec):
         raise TypeError(f"fss takes an FssSpec (got {type(spec).__name__})")
-    H, W = (x.shape[1:3] if x_nhwc else x.shape[2:4])
-    acc = FractionsSkill(spec, H, W, device=x.device, ops=ops)
+    acc = FractionsSkill(spec, H, W, device=device, ops=ops)
     return acc.add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

@@ -27,9 +27,9 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fields
 from .gridstats import SIDES, _jsonable, _side
-from .histograms import HistSpec, _default_ops, _descriptor, _fields
+from .histograms import HistSpec, _default_ops
 
 BINS_MAX = _lib.GRIDHIST_MAX_BINS
 Q_MAX = _lib.GRIDHIST_MAX_Q
@@ -295,15 +295,6 @@ class GridHist:
     def nbytes(self):
         return (self._buf.numel() - 1) * 4
 
-    def _series(self, x, nhwc, channels, what):
-        x, nhwc, Cn, T = _fields(x, channels, nhwc)
-        if Cn != self.spec.C:
-            raise ValueError(f"the HistSpec describes C = {self.spec.C} input channels but the {what} fields hold {Cn}")
-        hw = tuple(x.shape[1:3]) if nhwc else tuple(x.shape[2:4])
-        if hw != (self.H, self.W):
-            raise ValueError(f"GridHist was made for a {self.H} x {self.W} grid but the {what} fields are {hw[0]} x {hw[1]}")
-        return x, nhwc, Cn, T
-
     def add(self, real, fake=None, n_valid=None, nhwc=False, channels=None):
         """Add the first ``n_valid`` (default: all) fields of a batch: ``real`` alone, or the pair (real, fake) when this
         accumulator is paired.  Layouts as ``gridstats.GridStats.add`` ([T, C, H, W]; with ``nhwc`` a [T, H, W, c_pad] store
@@ -311,24 +302,14 @@ class GridHist:
         ``nhwc`` as a pair (real, fake) then."""
         if self.paired != (fake is not None):
             raise ValueError("a paired GridHist takes (real, fake)" if self.paired else "this GridHist takes one series (paired=False)")
-        fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-        if len(fl) != 2:
-            raise ValueError(f"nhwc is one flag or a (real, fake) pair (got {nhwc!r})")
-        a, a_nhwc, Cn, T = self._series(real, fl[0], channels, "real")
-        if self.paired:
-            b, b_nhwc, _, Tb = self._series(fake, fl[1], channels, "generated")
-            if Tb != T:
-                raise ValueError(f"real and generated batches differ in length ({T} and {Tb})")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "gridhist", self.spec, "GridHist", (self.H, self.W))
         if self._added + n >= FIELDS_MAX:
             raise ValueError(f"GridHist holds fewer than 2^26 fields: {self._added} + {n} would reach 2^26, where the scan's int64 sum "
                              "2 (bins + 1) n^2 reaches 2^63 (the table itself counts in int32)")
         if self._struct is None:
             self._struct = self.spec.struct()
-        ka, fa = _descriptor(self.ops, a[:n], a_nhwc, Cn)
-        kb, fb = _descriptor(self.ops, b[:n], b_nhwc, Cn) if self.paired else (None, None)
+        ka, fa = fields.descriptor(self.ops, a.x[:n], a.nhwc, a.C)
+        kb, fb = fields.descriptor(self.ops, b.x[:n], b.nhwc, b.C) if self.paired else (None, None)
         self.ops.gridhist(fa, fb, self._struct, self.counts)
         self._buf[-1] += n
         self._added += n
@@ -352,11 +333,9 @@ class GridHist:
 def gridhist(real, fake=None, spec=None, n_valid=None, nhwc=False, channels=None, ops=None):
     """Per-gridpoint histograms of one series of fields, or of a (real, fake) pair, on the GPU -> ``GridHistMaps``.  spec None:
     ``HistSpec.zscore(C, bins=64, lim=6.0)`` of the fields' channels; the other arguments as ``GridHist.add``."""
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    x, x_nhwc, Cn, _ = _fields(real, channels, fl[0])
+    Cn, H, W, device = fields.one_shot(real, nhwc, channels, "gridhist")
     if spec is None:
         spec = HistSpec.zscore(Cn, bins=64, lim=6.0)
     _check_spec(spec)
-    H, W = (x.shape[1:3] if x_nhwc else x.shape[2:4])
-    acc = GridHist(spec, H, W, paired=fake is not None, device=x.device, ops=ops)
+    acc = GridHist(spec, H, W, paired=fake is not None, device=device, ops=ops)
     return acc.add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

@@ -24,8 +24,8 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
-from .histograms import C_MAX, _default_ops, _descriptor, _f32, _fields
+from . import _lib, fields
+from .histograms import C_MAX, _default_ops, _f32
 
 THR_MAX = _lib.GRID_MAX_THR
 SIDES = ("real", "fake")
@@ -345,15 +345,6 @@ class GridStats:
     def fields(self):
         return int(self._nf.item())
 
-    def _series(self, x, nhwc, channels, what):
-        x, nhwc, Cn, T = _fields(x, channels, nhwc)
-        if Cn != self.spec.C:
-            raise ValueError(f"the GridSpec describes C = {self.spec.C} input channels but the {what} fields hold {Cn}")
-        hw = tuple(x.shape[1:3]) if nhwc else tuple(x.shape[2:4])
-        if hw != (self.H, self.W):
-            raise ValueError(f"GridStats was made for a {self.H} x {self.W} grid but the {what} fields are {hw[0]} x {hw[1]}")
-        return x, nhwc, Cn, T
-
     def add(self, real, fake=None, n_valid=None, nhwc=False, channels=None):
         """Add the first ``n_valid`` (default: all) fields of a batch: ``real`` alone, or the pair (real, fake) when this
         accumulator is paired.  Layouts as ``histograms.histogram`` ([T, C, H, W]; with ``nhwc`` a [T, H, W, c_pad] store of
@@ -361,23 +352,13 @@ class GridStats:
         ``nhwc`` as a pair (real, fake) then."""
         if self.paired != (fake is not None):
             raise ValueError("a paired GridStats takes (real, fake)" if self.paired else "this GridStats takes one series (paired=False)")
-        fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-        if len(fl) != 2:
-            raise ValueError(f"nhwc is one flag or a (real, fake) pair (got {nhwc!r})")
-        a, a_nhwc, Cn, T = self._series(real, fl[0], channels, "real")
-        if self.paired:
-            b, b_nhwc, _, Tb = self._series(fake, fl[1], channels, "generated")
-            if Tb != T:
-                raise ValueError(f"real and generated batches differ in length ({T} and {Tb})")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "gridstats", self.spec, "GridStats", (self.H, self.W))
         if self._added + n >= 2 ** 31:
             raise ValueError(f"GridStats counts in int32: {self._added} + {n} fields would reach 2^31")
         if self._struct is None:
             self._struct = self.spec.struct()
-        ka, fa = _descriptor(self.ops, a[:n], a_nhwc, Cn)
-        kb, fb = _descriptor(self.ops, b[:n], b_nhwc, Cn) if self.paired else (None, None)
+        ka, fa = fields.descriptor(self.ops, a.x[:n], a.nhwc, a.C)
+        kb, fb = fields.descriptor(self.ops, b.x[:n], b.nhwc, b.C) if self.paired else (None, None)
         self.ops.gridstats(fa, fb, self._struct, self._sums, self._ext, self._cnt)
         self._nf += n
         self._added += n
@@ -406,12 +387,10 @@ class GridStats:
 def gridstats(real, fake=None, spec=None, n_valid=None, nhwc=False, channels=None, ops=None):
     """Per-gridpoint statistics of one series of fields, or of a (real, fake) pair, on the GPU -> ``GridMaps``.  spec None:
     ``GridSpec.zscore`` of the fields' channels; the other arguments as ``GridStats.add``."""
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    x, x_nhwc, Cn, _ = _fields(real, channels, fl[0])
+    Cn, H, W, device = fields.one_shot(real, nhwc, channels, "gridstats")
     if spec is None:
         spec = GridSpec.zscore(Cn)
     if not isinstance(spec, GridSpec):
         raise TypeError(f"gridstats takes a GridSpec (got {type(spec).__name__})")
-    H, W = (x.shape[1:3] if x_nhwc else x.shape[2:4])
-    acc = GridStats(spec, H, W, paired=fake is not None, device=x.device, ops=ops)
+    acc = GridStats(spec, H, W, paired=fake is not None, device=device, ops=ops)
     return acc.add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

@@ -24,7 +24,8 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, backend
+from . import _lib
+from .fields import agree, default_ops, descriptor as _descriptor, n_valid as _n_valid, series
 
 BINS_MAX = _lib.HIST_MAX_BINS
 C_MAX = _lib.EOF_MAX_C
@@ -33,10 +34,7 @@ _ops = {}                    # device -> op backend of the module-level calls
 
 
 def _default_ops(device):
-    key = str(device)
-    if key not in _ops:
-        _ops[key] = backend.make_ops("f32", device)
-    return _ops[key]
+    return default_ops(_ops, device)
 
 
 def _f32(v, what):
@@ -151,50 +149,15 @@ def host_bins(spec, x):
 
 
 def _fields(x, channels, nhwc):
-    """Validate without touching a device -> (tensor, nhwc, C, T)."""
-    if hasattr(x, "nhwc") and hasattr(x, "channels"):          # dataloader.NativeBatch
-        x, nhwc, channels = x.nhwc, True, x.channels if channels is None else channels
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"histogram takes a tensor or a NativeBatch (got {type(x).__name__})")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"histogram reads fp32 or bf16 fields (got {x.dtype})")
-    if x.dim() != 4:
-        raise ValueError(f"histogram takes [T, C, H, W] (or [T, H, W, c] with nhwc=True) fields (got shape {tuple(x.shape)})")
-    if nhwc:
-        T, H, W, cp = x.shape
-        Cn = cp if channels is None else int(channels)
-        if not 1 <= Cn <= cp:
-            raise ValueError(f"channels = {Cn} but the NHWC store holds {cp}")
-    else:
-        T, cx, H, W = x.shape
-        Cn = cx if channels is None else int(channels)
-        if not 1 <= Cn <= cx:
-            raise ValueError(f"channels = {Cn} but the tensor holds {cx}")
-    if not 1 <= Cn <= C_MAX:
-        raise ValueError(f"histogram takes 1 <= C <= {C_MAX} channels (got C = {Cn})")
-    if T < 1 or H * W < 1:
-        raise ValueError(f"histogram needs at least one field of at least one pixel (got shape {tuple(x.shape)})")
-    if H * W >= 2 ** 31 or T >= 2 ** 31:
-        raise ValueError(f"histogram takes fewer than 2^31 fields of fewer than 2^31 pixels (got shape {tuple(x.shape)})")
-    return x, nhwc, Cn, int(T)
+    """Validate without touching a device -> (tensor, nhwc, C, T).  Kept under this name, as ``_descriptor`` and ``_default_ops``
+    are, for the GPU tests and tools that call the kernels directly."""
+    return series(x, channels, nhwc, "histogram")[:4]
 
 
-def _check_spec(spec, Cn):
+def _check_spec(spec, s):
     if not isinstance(spec, HistSpec):
         raise TypeError(f"histogram takes a HistSpec (got {type(spec).__name__})")
-    if spec.C != Cn:
-        raise ValueError(f"the HistSpec describes C = {spec.C} input channels but the fields hold {Cn}")
-
-
-def _descriptor(o, x, nhwc, Cn):
-    if nhwc:
-        if not (x.stride(3) == 1 and x.stride(2) == x.shape[3] and x.stride(1) == x.shape[2] * x.shape[3]):
-            x = x.contiguous()
-        return x, o.eof_fields(x, nhwc=True, channels=Cn)
-    x = x[:, :Cn]
-    if not (x.stride(3) == 1 and x.stride(2) == x.shape[3] and x.stride(1) == x.shape[2] * x.shape[3]):
-        x = x.contiguous()
-    return x, o.eof_fields(x)
+    agree(s, spec, "given")
 
 
 class Histogram:
@@ -308,9 +271,9 @@ def histogram(x, spec, channels=None, nhwc=False, ops=None):
     x: device tensor [T, C, H, W] (fp32 / bf16), or with ``nhwc`` a dense-pixel [T, H, W, c_pad] store of which the leading
     ``channels`` are read (the generator's padded output; default: all), or a ``dataloader.NativeBatch``.  Returns a
     ``Histogram`` over every value of the T fields."""
-    x, nhwc, Cn, T = _fields(x, channels, nhwc)
-    _check_spec(spec, Cn)
-    return ValueHistogram(spec, x.device, ops=ops).add(x, nhwc=nhwc, channels=Cn).result()
+    s = series(x, channels, nhwc, "histogram")
+    _check_spec(spec, s)
+    return ValueHistogram(spec, s.x.device, ops=ops).add(s.x, nhwc=s.nhwc, channels=s.C).result()
 
 
 def _pair(a, b):
@@ -383,14 +346,12 @@ class ValueHistogram:
 
     def add(self, fields, n_valid=None, nhwc=False, channels=None):
         """Add every value of the first ``n_valid`` (default: all) fields of a batch (layouts as ``histogram``)."""
-        x, nhwc, Cn, T = _fields(fields, channels, nhwc)
-        _check_spec(self.spec, Cn)
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        s = series(fields, channels, nhwc, "histogram")
+        _check_spec(self.spec, s)
+        n = _n_valid(n_valid, s.T)
         if self._struct is None:
             self._struct = self.spec.struct()
-        xs, f = _descriptor(self.ops, x[:n], nhwc, Cn)
+        xs, f = _descriptor(self.ops, s.x[:n], s.nhwc, s.C)
         self.ops.hist(f, self._struct, self.counts, self._mom, self._ext)
         self._cnt[-1] += n
         return self

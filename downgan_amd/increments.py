@@ -26,9 +26,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, backend
+from . import _lib, fields
 from .fss import allreduce_ints
-from .histograms import C_MAX, Histogram, HistSpec, _descriptor, _f32, _fields, ks_distance, wasserstein1
+from .histograms import C_MAX, Histogram, HistSpec, _f32, ks_distance, wasserstein1
 
 LAGS_MAX = _lib.INCR_MAX_LAGS
 LAG_MAX = _lib.INCR_MAX_LAG
@@ -41,10 +41,7 @@ _ops = {}                    # device -> op backend of the module-level calls
 
 
 def _default_ops(device):
-    key = str(device)
-    if key not in _ops:
-        _ops[key] = backend.make_ops("f32", device)
-    return _ops[key]
+    return fields.default_ops(_ops, device)
 
 
 def _int(v):
@@ -351,40 +348,6 @@ class IncrementResult:
         return out
 
 
-def _flags(nhwc):
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    if len(fl) != 2:
-        raise ValueError(f"nhwc is one flag or a (real, fake) pair (got {nhwc!r})")
-    return fl
-
-
-def _series(spec, a, b, n_valid, nhwc, channels):
-    """Validate without touching a device -> (a, a_nhwc, b | None, b_nhwc, C, n, (H, W))."""
-    fl = _flags(nhwc)
-    a, a_nhwc, Cn, T = _fields(a, channels, fl[0])
-    if spec.C != Cn:
-        raise ValueError(f"the IncrementSpec describes C = {spec.C} input channels but the fields hold {Cn}")
-    hw = lambda x, f: tuple(int(v) for v in (x.shape[1:3] if f else x.shape[2:4]))
-    grid = hw(a, a_nhwc)
-    if not all(1 <= v <= SIDE_MAX for v in grid):
-        raise ValueError(f"increment histograms take grids of 1 <= H, W <= {SIDE_MAX} (got {grid[0]} x {grid[1]})")
-    b_nhwc = False
-    if b is not None:
-        b, b_nhwc, Cb, Tb = _fields(b, channels, fl[1])
-        if Cb != Cn:
-            raise ValueError(f"the two series differ in channels ({Cn} and {Cb})")
-        if Tb != T:
-            raise ValueError(f"the two series differ in length ({T} and {Tb})")
-        if hw(b, b_nhwc) != grid:
-            raise ValueError(f"the two series differ in grid ({grid} and {hw(b, b_nhwc)})")
-        if b.device != a.device:
-            raise ValueError(f"the two series live on different devices ({a.device} and {b.device})")
-    n = T if n_valid is None else int(n_valid)
-    if not 1 <= n <= T:
-        raise ValueError(f"n_valid = {n} of a batch of {T}")
-    return a, a_nhwc, b, b_nhwc, Cn, n, grid
-
-
 class Increments:
     """Running increment histograms of the fields added so far: counts, finite and moments stay on the device (two series'
     worth; a run without generated fields uses the first half).  Every ``add`` of one accumulator takes the same grid and either
@@ -416,8 +379,10 @@ class Increments:
         (real, generated).  Layouts as ``histograms.histogram`` ([T, C, H, W] fp32 / bf16; with ``nhwc`` a [T, H, W, c_pad]
         store of which the leading ``channels`` are read; a ``NativeBatch``); the two series may differ in layout and dtype:
         pass ``nhwc`` as a (real, fake) pair then."""
-        a, a_nhwc, b, b_nhwc, Cn, n, grid = _series(self.spec, real, fake, n_valid, nhwc, channels)
-        nser = 1 if b is None else 2
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "increment histograms", self.spec)
+        nser, grid = 1 if b is None else 2, (a.H, a.W)
+        if not all(1 <= v <= SIDE_MAX for v in grid):
+            raise ValueError(f"increment histograms take grids of 1 <= H, W <= {SIDE_MAX} (got {grid[0]} x {grid[1]})")
         if self.nser not in (None, nser):
             raise ValueError(f"this accumulator holds {self.nser} series per add (got {nser})")
         if self.grid not in (None, grid):
@@ -427,8 +392,8 @@ class Increments:
             self._struct = self.spec.struct()
         o, (H, W) = self.ops, grid
         # one call for the whole batch: dg_incr's workspace is a fixed number of per-workgroup slots, whatever the field count
-        ka, fa = _descriptor(o, a[:n], a_nhwc, Cn)
-        kb, fb = _descriptor(o, b[:n], b_nhwc, Cn) if b is not None else (None, None)
+        ka, fa = fields.descriptor(o, a.x[:n], a.nhwc, a.C)
+        kb, fb = fields.descriptor(o, b.x[:n], b.nhwc, b.C) if b is not None else (None, None)
         o.incr(fa, fb, H, W, self._struct, self._cnt[:nser], self._fin[:nser], self._mom[:nser])
         self.fields += n
         return self
@@ -459,7 +424,7 @@ def increments(real, fake=None, spec=None, n_valid=None, nhwc=False, channels=No
     ``IncrementSpec.zscore`` of the fields' channels; the other arguments as ``Increments.add``."""
     if spec is not None and not isinstance(spec, IncrementSpec):
         raise TypeError(f"increments takes an IncrementSpec (got {type(spec).__name__})")
-    x, _, Cn, _ = _fields(real, channels, _flags(nhwc)[0])
+    Cn, _, _, device = fields.one_shot(real, nhwc, channels, "increment histograms")
     if spec is None:
         spec = IncrementSpec.zscore(Cn)
-    return Increments(spec, x.device, ops=ops).add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()
+    return Increments(spec, device, ops=ops).add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

@@ -43,8 +43,8 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, backend
-from .histograms import C_MAX, _descriptor, _f32, _fields
+from . import _lib, fields
+from .histograms import C_MAX, _f32
 
 PAIRS_MAX = _lib.HIST2D_MAX_PAIRS
 CELLS_MAX = _lib.HIST2D_MAX_CELLS
@@ -54,10 +54,7 @@ _ops = {}                    # device -> op backend of the module-level calls
 
 
 def _default_ops(device):
-    key = str(device)
-    if key not in _ops:
-        _ops[key] = backend.make_ops("f32", device)
-    return _ops[key]
+    return fields.default_ops(_ops, device)
 
 
 class Axis:
@@ -470,43 +467,12 @@ class Joint:
         return out
 
 
-def _check_spec(spec, Cn):
-    if not isinstance(spec, JointSpec):
-        raise TypeError(f"joint histograms take a JointSpec (got {type(spec).__name__})")
-    if spec.C != Cn:
-        raise ValueError(f"the JointSpec describes C = {spec.C} input channels but the fields hold {Cn}")
-
-
-def _flags(nhwc):
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    if len(fl) != 2:
-        raise ValueError(f"nhwc is one flag or an (a, b) pair (got {nhwc!r})")
-    return fl
-
-
-def _series(spec, a, b, n_valid, nhwc, channels):
-    """Validate without touching a device -> (a, a_nhwc, b | None, b_nhwc, C, n)."""
-    fl = _flags(nhwc)
-    a, a_nhwc, Cn, T = _fields(a, channels, fl[0])
-    _check_spec(spec, Cn)
-    b_nhwc = False
-    if b is not None:
-        b, b_nhwc, Cb, Tb = _fields(b, channels, fl[1])
-        if Cb != Cn:
-            raise ValueError(f"the two series differ in channels ({Cn} and {Cb})")
-        if Tb != T:
-            raise ValueError(f"the two series differ in length ({T} and {Tb})")
-        hw = lambda x, f: tuple(x.shape[1:3]) if f else tuple(x.shape[2:4])
-        if hw(a, a_nhwc) != hw(b, b_nhwc):
-            raise ValueError(f"the two series differ in grid ({hw(a, a_nhwc)} and {hw(b, b_nhwc)})")
-        if b.device != a.device:
-            raise ValueError(f"the two series live on different devices ({a.device} and {b.device})")
-    elif spec.uses_b:
+def _batch(spec, a, b, n_valid, nhwc, channels):
+    """Validate without touching a device -> (a Series, b Series | None, n)."""
+    a, b, n = fields.batch(a, b, nhwc, channels, n_valid, "joint histograms", spec, sides=("a", "b"))
+    if b is None and spec.uses_b:
         raise ValueError("the JointSpec has an axis of series b but b is None")
-    n = T if n_valid is None else int(n_valid)
-    if not 1 <= n <= T:
-        raise ValueError(f"n_valid = {n} of a batch of {T}")
-    return a, a_nhwc, b, b_nhwc, Cn, n
+    return a, b, n
 
 
 class ValueJoint:
@@ -541,12 +507,12 @@ class ValueJoint:
         Layouts as ``histograms.histogram`` ([T, C, H, W] fp32 / bf16; with ``nhwc`` a [T, H, W, c_pad] store of which the
         leading ``channels`` are read; a ``NativeBatch``); the two series may differ in layout and dtype: pass ``nhwc`` as an
         (a, b) pair then."""
-        a, a_nhwc, b, b_nhwc, Cn, n = _series(self.spec, a, b, n_valid, nhwc, channels)
+        a, b, n = _batch(self.spec, a, b, n_valid, nhwc, channels)
         if self._struct is None:
             self._struct = self.spec.struct()
         o = self.ops
-        xa, fa = _descriptor(o, a[:n], a_nhwc, Cn)
-        xb, fb = _descriptor(o, b[:n], b_nhwc, Cn) if b is not None else (None, None)
+        xa, fa = fields.descriptor(o, a.x[:n], a.nhwc, a.C)
+        xb, fb = fields.descriptor(o, b.x[:n], b.nhwc, b.C) if b is not None else (None, None)
         o.hist2d(fa, fb, self._struct, self.counts)
         self._cnt[-1] += n
         return self
@@ -567,5 +533,5 @@ def joint_histogram(a, spec, b=None, channels=None, nhwc=False, ops=None):
     The arguments as ``ValueJoint.add``."""
     if not isinstance(spec, JointSpec):
         raise TypeError(f"joint histograms take a JointSpec (got {type(spec).__name__})")
-    x = _series(spec, a, b, None, nhwc, channels)[0]
-    return ValueJoint(spec, x.device, ops=ops).add(a, b, nhwc=nhwc, channels=channels).result()
+    device = _batch(spec, a, b, None, nhwc, channels)[0].x.device
+    return ValueJoint(spec, device, ops=ops).add(a, b, nhwc=nhwc, channels=channels).result()

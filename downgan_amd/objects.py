@@ -33,10 +33,10 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fields
 from .fss import allreduce_ints
 from .gridstats import _jsonable
-from .histograms import C_MAX, _default_ops, _descriptor, _f32, _fields
+from .histograms import C_MAX, _default_ops, _f32
 
 THR_MAX, SIDE_MAX, COLS = _lib.OBJ_MAX_THR, _lib.OBJ_MAX_SIDE, _lib.OBJ_COLS
 WS_CAP = 512 << 20           # bytes of dg_objects workspace at most: a batch is cut into chunks of fields (at least one)
@@ -363,15 +363,6 @@ class Objects:
             self._ops = _default_ops(self.device)
         return self._ops
 
-    def _series(self, x, nhwc, channels, what):
-        x, nhwc, Cn, T = _fields(x, channels, nhwc)
-        if Cn != self.spec.C:
-            raise ValueError(f"the ObjectSpec describes C = {self.spec.C} input channels but the {what} fields hold {Cn}")
-        hw = tuple(x.shape[1:3]) if nhwc else tuple(x.shape[2:4])
-        if hw != (self.H, self.W):
-            raise ValueError(f"Objects was made for a {self.H} x {self.W} grid but the {what} fields are {hw[0]} x {hw[1]}")
-        return x, nhwc, Cn, T
-
     def _pool(self, rec, m):
         """Pool the sorted records int64 [n, 12] of a chunk of ``m`` fields."""
         sp, ns = self.spec, 2 if self.paired else 1
@@ -430,30 +421,20 @@ class Objects:
         with one synchronising copy of its object count; a table that was too small is grown and the call repeated."""
         if (fake is not None) != self.paired:
             raise ValueError("a paired Objects takes (real, fake), an unpaired one real alone")
-        fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-        if len(fl) != 2:
-            raise ValueError(f"nhwc is one flag or a (real, fake) pair (got {nhwc!r})")
-        a, a_nhwc, Cn, T = self._series(real, fl[0], channels, "real")
-        if self.paired:
-            b, b_nhwc, _, Tb = self._series(fake, fl[1], channels, "generated")
-            if Tb != T:
-                raise ValueError(f"real and generated batches differ in length ({T} and {Tb})")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "objects", self.spec, "Objects", (self.H, self.W))
         if self._struct is None:
             self._struct = self.spec.struct()
         o = self.ops
-        _, f1 = _descriptor(o, a[:1], a_nhwc, Cn)
+        _, f1 = fields.descriptor(o, a.x[:1], a.nhwc, a.C)
         per_field = max(1, o.objects_ws_bytes(f1, self.H, self.W, self._struct))
         most = 2 * self.spec.nout * self.spec.K * ((self.H * self.W + 1) // 2)       # objects of one field at most
         tc = max(1, min(n, WS_CAP // per_field, (SLOT_LIMIT - 1) // most))
         for t0 in range(0, n, tc):
             m = min(tc, n - t0)
-            ka, fa = _descriptor(o, a[t0:t0 + m], a_nhwc, Cn)
+            ka, fa = fields.descriptor(o, a.x[t0:t0 + m], a.nhwc, a.C)
             fb = None
             if self.paired:
-                kb, fb = _descriptor(o, b[t0:t0 + m], b_nhwc, Cn)
+                kb, fb = fields.descriptor(o, b.x[t0:t0 + m], b.nhwc, b.C)
             table, _, calls = o.objects(fa, fb, self.H, self.W, self._struct)
             self.calls += calls
             self._pool(table.cpu().numpy(), m)
@@ -497,12 +478,10 @@ class Objects:
 def objects(real, fake=None, spec=None, n_valid=None, nhwc=False, channels=None, ops=None, keep_records=False):
     """Object statistics of a series of fields, or of a (real, generated) pair of series, on the GPU -> ``ObjectsResult``.  spec
     None: ``ObjectSpec.zscore`` of the fields' channels; the other arguments as ``Objects.add``."""
-    fl = tuple(nhwc) if isinstance(nhwc, (tuple, list)) else (nhwc, nhwc)
-    x, x_nhwc, Cn, _ = _fields(real, channels, fl[0])
+    Cn, H, W, device = fields.one_shot(real, nhwc, channels, "objects")
     if spec is None:
         spec = ObjectSpec.zscore(Cn)
     if not isinstance(spec, ObjectSpec):
         raise TypeError(f"objects takes an ObjectSpec (got {type(spec).__name__})")
-    H, W = (x.shape[1:3] if x_nhwc else x.shape[2:4])
-    acc = Objects(spec, H, W, paired=fake is not None, device=x.device, ops=ops, keep_records=keep_records)
+    acc = Objects(spec, H, W, paired=fake is not None, device=device, ops=ops, keep_records=keep_records)
     return acc.add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

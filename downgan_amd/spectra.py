@@ -35,7 +35,8 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, backend
+from . import _lib
+from .fields import default_ops, descriptor as _descriptor, n_valid as _n_valid, pair as _paired, series
 
 N_MIN, N_MAX = 16, _lib.RAPSD_MAX_N
 C_MAX = _lib.EOF_MAX_C
@@ -45,10 +46,7 @@ _ops = {}                    # device -> op backend of the module-level calls
 
 
 def _default_ops(device):
-    key = str(device)
-    if key not in _ops:
-        _ops[key] = backend.make_ops("f32", device)
-    return _ops[key]
+    return default_ops(_ops, device)
 
 
 def check_n(N):
@@ -72,44 +70,12 @@ def ring_counts(N):
 
 
 def _fields(x, channels, nhwc):
-    """Validate without touching a device -> (tensor, nhwc, C, T, N)."""
-    if hasattr(x, "nhwc") and hasattr(x, "channels"):          # dataloader.NativeBatch
-        x, nhwc, channels = x.nhwc, True, x.channels if channels is None else channels
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"RAPSD takes a tensor or a NativeBatch (got {type(x).__name__})")
-    if x.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"RAPSD reads fp32 or bf16 fields (got {x.dtype})")
-    if x.dim() != 4:
-        raise ValueError(f"RAPSD takes [T, C, N, N] (or [T, N, N, c] with nhwc=True) fields (got shape {tuple(x.shape)})")
-    if nhwc:
-        T, H, W, cp = x.shape
-        Cn = cp if channels is None else int(channels)
-        if not 1 <= Cn <= cp:
-            raise ValueError(f"channels = {Cn} but the NHWC store holds {cp}")
-    else:
-        T, cx, H, W = x.shape
-        Cn = cx if channels is None else int(channels)
-        if not 1 <= Cn <= cx:
-            raise ValueError(f"channels = {Cn} but the tensor holds {cx}")
-    if H != W:
-        raise ValueError(f"RAPSD needs square fields (got {H} x {W})")
-    check_n(int(H))
-    if not 1 <= Cn <= C_MAX:
-        raise ValueError(f"RAPSD takes 1 <= C <= {C_MAX} channels (got C = {Cn})")
-    if T < 1:
-        raise ValueError("RAPSD needs at least one field")
-    return x, nhwc, Cn, int(T), int(H)
-
-
-def _descriptor(o, x, nhwc, Cn):
-    if nhwc:
-        if not (x.stride(3) == 1 and x.stride(2) == x.shape[3] and x.stride(1) == x.shape[2] * x.shape[3]):
-            x = x.contiguous()
-        return x, o.eof_fields(x, nhwc=True, channels=Cn)
-    x = x[:, :Cn]
-    if not (x.stride(3) == 1 and x.stride(2) == x.shape[3] and x.stride(1) == x.shape[2] * x.shape[3]):
-        x = x.contiguous()
-    return x, o.eof_fields(x)
+    """Validate without touching a device -> the ``fields.Series`` (tensor, nhwc, C, T, N, N)."""
+    s = series(x, channels, nhwc, "RAPSD")
+    if s.H != s.W:
+        raise ValueError(f"RAPSD needs square fields (got {s.H} x {s.W})")
+    check_n(s.H)
+    return s
 
 
 def _chunk(o, T, Cn, N):
@@ -136,7 +102,7 @@ def rapsd(x, channels=None, nhwc=False, per_field=False, ops=None):
     x: device tensor [T, C, N, N] (fp32 / bf16), or with ``nhwc`` a dense-pixel [T, N, N, c_pad] store of which the leading
     ``channels`` are read (the generator's padded output; default: all), or a ``dataloader.NativeBatch``.
     Returns float64 [C, N/2 + 1], the mean over T, or [T, C, N/2 + 1] with ``per_field``."""
-    x, nhwc, Cn, T, N = _fields(x, channels, nhwc)
+    x, nhwc, Cn, T, N = _fields(x, channels, nhwc)[:5]
     o = ops if ops is not None else _default_ops(x.device)
     K = N // 2 + 1
     if per_field:
@@ -164,13 +130,9 @@ def log_spectral_distance(p_ref, p, kmin=1):
 
 def _pair(a, b, channels, nhwc, nhwc_b):
     """Validate both sides and their agreement without touching a device -> ((a, nhwc_a), (b, nhwc_b), C, T, N)."""
-    a, na, Ca, Ta, Na = _fields(a, channels, nhwc)
-    b, nb, Cb, Tb, Nb = _fields(b, channels, nhwc if nhwc_b is None else nhwc_b)
-    if (Ta, Ca, Na) != (Tb, Cb, Nb):
-        raise ValueError(f"cross spectra need paired fields: a has T, C, N = {Ta}, {Ca}, {Na} and b has {Tb}, {Cb}, {Nb}")
-    if a.device != b.device:
-        raise ValueError(f"cross spectra need both sides on one device (got {a.device} and {b.device})")
-    return (a, na), (b, nb), Ca, Ta, Na
+    a, b = _fields(a, channels, nhwc), _fields(b, channels, nhwc if nhwc_b is None else nhwc_b)
+    _paired(a, b, ("a", "b"))
+    return a[:2], b[:2], a.C, a.T, a.H
 
 
 def _cross_chunk(o, T, Cn, N):
@@ -307,9 +269,7 @@ class CrossSpectrum:
         sa, sb, Cn, T, N = _pair(a, b, channels, nhwc, nhwc_b)
         if (Cn, N) != (self.C, self.N):
             raise ValueError(f"CrossSpectrum({self.C}, {self.N}) given {Cn} channels of {N} x {N}")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        n = _n_valid(n_valid, T)
         _cross_sum_into(self.ops, (sa[0][:n], sa[1]), (sb[0][:n], sb[1]), Cn, n, N, self.sums)
         self._acc[-1] += n
         return self
@@ -361,12 +321,10 @@ class RadialSpectrum:
 
     def add(self, fields, n_valid=None, nhwc=False, channels=None):
         """Add the spectra of the first ``n_valid`` (default: all) fields of a batch (layouts as ``rapsd``)."""
-        x, nhwc, Cn, T, N = _fields(fields, channels, nhwc)
+        x, nhwc, Cn, T, N = _fields(fields, channels, nhwc)[:5]
         if (Cn, N) != (self.C, self.N):
             raise ValueError(f"RadialSpectrum({self.C}, {self.N}) given {Cn} channels of {N} x {N}")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        n = _n_valid(n_valid, T)
         _sum_into(self.ops, x[:n], nhwc, Cn, n, N, self.sums)
         self._acc[-1] += n
         return self
@@ -419,7 +377,7 @@ def _helm_scale(scale, rows_up):
 
 
 def _helm_fields(x, channels, nhwc, pair):
-    x, nhwc, Cn, T, N = _fields(x, channels, nhwc)
+    x, nhwc, Cn, T, N = _fields(x, channels, nhwc)[:5]
     if Cn < 2:
         raise ValueError(f"Helmholtz spectra need a vector field: C >= 2 channels (got C = {Cn})")
     return x, nhwc, Cn, T, N, _helm_pair(pair, Cn)
@@ -597,9 +555,7 @@ class HelmholtzSpectrum:
         sa, sb, Cn, T, N, (cu, cv) = _helm_sides(a, b, self.pair, nhwc, nhwc_b, channels)
         if N != self.N:
             raise ValueError(f"HelmholtzSpectrum({self.N}) given fields of {N} x {N}")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        n = _n_valid(n_valid, T)
         _helm_run(self.ops, (sa[0][:n], sa[1]), (sb[0][:n], sb[1]), Cn, n, N, cu, cv, self.scale, total=self.sums)
         self._acc[-1] += n
         return self

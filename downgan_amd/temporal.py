@@ -30,10 +30,10 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, fields
 from .gridstats import SIDES, _side
-from .histograms import C_MAX, Histogram, HistSpec, _default_ops, _descriptor, _f32, _fields, ks_distance, wasserstein1
-from .increments import _flags, _int, _jsonable, _ratio
+from .histograms import C_MAX, Histogram, HistSpec, _default_ops, _f32, ks_distance, wasserstein1
+from .increments import _int, _jsonable, _ratio
 
 THR_MAX = _lib.TEMPORAL_MAX_THR
 DUR_MAX = _lib.TEMPORAL_MAX_DUR
@@ -489,15 +489,6 @@ class Temporal:
     def nbytes(self):
         return sum(a.numel() * a.element_size() for a in self.arrays.values())
 
-    def _series(self, x, nhwc, channels, what):
-        x, nhwc, Cn, T = _fields(x, channels, nhwc)
-        if Cn != self.spec.C:
-            raise ValueError(f"the TemporalSpec describes C = {self.spec.C} input channels but the {what} fields hold {Cn}")
-        hw = tuple(x.shape[1:3]) if nhwc else tuple(x.shape[2:4])
-        if hw != (self.H, self.W):
-            raise ValueError(f"Temporal was made for a {self.H} x {self.W} grid but the {what} fields are {hw[0]} x {hw[1]}")
-        return x, nhwc, Cn, T
-
     def add(self, real, fake=None, n_valid=None, nhwc=False, channels=None):
         """Add the first ``n_valid`` (default: all) fields of a batch as the next times of the series: ``real`` alone, or the
         pair (real, fake) when this accumulator is paired.  Layouts as ``gridhist.GridHist.add`` ([T, C, H, W]; with ``nhwc`` a
@@ -505,20 +496,12 @@ class Temporal:
         layout and dtype: pass ``nhwc`` as a pair (real, fake) then."""
         if self.paired != (fake is not None):
             raise ValueError("a paired Temporal takes (real, fake)" if self.paired else "this Temporal takes one series (paired=False)")
-        fl = _flags(nhwc)
-        a, a_nhwc, Cn, T = self._series(real, fl[0], channels, "real")
-        if self.paired:
-            b, b_nhwc, _, Tb = self._series(fake, fl[1], channels, "generated")
-            if Tb != T:
-                raise ValueError(f"real and generated batches differ in length ({T} and {Tb})")
-        n = T if n_valid is None else int(n_valid)
-        if not 1 <= n <= T:
-            raise ValueError(f"n_valid = {n} of a batch of {T}")
+        a, b, n = fields.batch(real, fake, nhwc, channels, n_valid, "temporal diagnostics", self.spec, "Temporal", (self.H, self.W))
         _check_time(self.fields, n)
         if self._struct is None:
             self._struct = self.spec.struct()
-        ka, fa = _descriptor(self.ops, a[:n], a_nhwc, Cn)
-        kb, fb = _descriptor(self.ops, b[:n], b_nhwc, Cn) if self.paired else (None, None)
+        ka, fa = fields.descriptor(self.ops, a.x[:n], a.nhwc, a.C)
+        kb, fb = fields.descriptor(self.ops, b.x[:n], b.nhwc, b.C) if self.paired else (None, None)
         self.ops.temporal(fa, fb, self._struct, self.fields, *[self.arrays[k] for k in ARRAYS])
         self.fields += n
         return self
@@ -535,10 +518,9 @@ class Temporal:
 def temporal(real, fake=None, spec=None, n_valid=None, nhwc=False, channels=None, ops=None):
     """Temporal diagnostics of one series of fields in time order, or of a (real, fake) pair, on the GPU -> ``TemporalResult``.
     spec None: ``TemporalSpec.zscore`` of the fields' channels; the other arguments as ``Temporal.add``."""
-    x, x_nhwc, Cn, _ = _fields(real, channels, _flags(nhwc)[0])
+    Cn, H, W, device = fields.one_shot(real, nhwc, channels, "temporal diagnostics")
     if spec is None:
         spec = TemporalSpec.zscore(Cn)
     _check_spec(spec)
-    H, W = (x.shape[1:3] if x_nhwc else x.shape[2:4])
-    acc = Temporal(spec, H, W, paired=fake is not None, device=x.device, ops=ops)
+    acc = Temporal(spec, H, W, paired=fake is not None, device=device, ops=ops)
     return acc.add(real, fake, n_valid=n_valid, nhwc=nhwc, channels=channels).result()

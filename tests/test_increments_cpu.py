@@ -335,7 +335,10 @@ def test_abi_rejects_bad_arguments_without_launching():
     for i, s in enumerate(bad_specs):
         assert call(f(), f(), s) == -1, i
         assert lib.dg_incr_ws_bytes(f(), f(), 10, 10, s) == 0, i
-    assert call(f(), None, spec(speed_u=-1, speed_v=-1)) in (0, -4)              # no speed channel: valid (no GPU here: a launch error)
+    no_speed = spec(speed_u=-1, speed_v=-1)
+    assert lib.dg_incr_ws_bytes(f(), None, 10, 10, no_speed) > 0                  # no speed channel: valid for the one validator
+    if not torch.cuda.is_available():                                            # valid arguments launch: only without a device,
+        assert call(f(), None, no_speed) == -4                                   # where that is the launch error
     for fa, fb, H, W in ((None, f(), 10, 10), (f(base=0), None, 10, 10), (f(), f(base=0), 10, 10), (f(C=9), None, 10, 10),
                          (f(T=0), None, 10, 10), (f(), None, 10, 11), (f(), None, 5, 10), (f(), None, 0, 10),
                          (f(P=2049), None, 1, 2049), (f(P=2049), None, 2049, 1),
