@@ -58,7 +58,15 @@ static void wg_group_order(WGArgs& a, int nco_t, int ntiles, int splits) {
 // number of workgroups of a grouped launch: every XCD gets the same number of unit slots
 static unsigned wg_group_blocks(const WGArgs& a) { return 8u * (unsigned)((a.nunits + 7) / 8) * (unsigned)a.grp; }
 
-// decode of a workgroup's (tile, pixel split); false = a padding workgroup of a grouped launch
+// (tile bx, pixel split by) of a workgroup of a (tiles, splits) grid.
+// XCD-aware remap of the linear workgroup id: the 9 tap-workgroups (and channel tiles) of one pixel range become
+// consecutive ids on ONE XCD, so the tiles they all re-read are served by that XCD's L2 instead of the fabric
+// (measured: +15-35 % on layers with <= 72 tiles per pixel range, -5-12 % on the widest layers, hence the gate)
+__device__ __forceinline__ void wg_decode_grid(unsigned lin0, int& bx, int& by) {
+  const unsigned lin = gridDim.x <= 72 ? xcd_remap(lin0, gridDim.x * gridDim.y) : lin0;
+  bx = (int)(lin % gridDim.x); by = (int)(lin / gridDim.x);
+}
+// the same for the wide kernels, whose launch may be grouped; false = a padding workgroup of a grouped launch
 __device__ __forceinline__ bool wg_decode(const WGArgs& a, int& bx, int& by) {
   const unsigned lin0 = blockIdx.y * gridDim.x + blockIdx.x;
   if (a.grp) {
@@ -68,9 +76,25 @@ __device__ __forceinline__ bool wg_decode(const WGArgs& a, int& bx, int& by) {
     by = (int)(unit / (unsigned)a.ngrp); bx = (int)((unit % (unsigned)a.ngrp) * (unsigned)a.grp + within);
     return true;
   }
-  const unsigned lin = gridDim.x <= 72 ? xcd_remap(lin0, gridDim.x * gridDim.y) : lin0;
-  bx = (int)(lin % gridDim.x); by = (int)(lin / gridDim.x);
+  wg_decode_grid(lin0, bx, by);
   return true;
+}
+// row-of-taps tile bx -> (adjoint tile, input tile, tap row); the input tile is the fastest coordinate
+__device__ __forceinline__ void wg_decode_tile(const WGArgs& a, int bx, int& co_t, int& ci_t, int& trow) {
+  ci_t = bx % a.nci_t;
+  trow = (bx / a.nci_t) % 3;
+  co_t = bx / (a.nci_t * 3);
+}
+// ... of the wide kernels, with their dense-block mode
+__device__ __forceinline__ void wg_decode_tile_wide(const WGArgs& a, int bx, int& co_t, int& ci_t, int& trow) {
+  wg_decode_tile(a, bx, co_t, ci_t, trow);
+  if (a.tri) {                                    // bx = 3 * pair + tap row; pair p = t (t + 1) / 2 + input tile, input tile <= t
+    trow = bx % 3;
+    const int p = bx / 3;
+    co_t = 0;
+    while ((co_t + 1) * (co_t + 2) / 2 <= p) ++co_t;
+    ci_t = p - co_t * (co_t + 1) / 2;
+  }
 }
 #define WG_DET_PTR(a, p, by) ((a).det_ws ? (a).det_ws + (long long)(by) * (a).det_stride + ((p) - (a).det_base) : (p))
 #define WG_DET_DB(a, by) ((a).det_ws ? (a).det_ws + (long long)(by) * (a).det_stride + (a).det_db_off : (a).db)
@@ -79,6 +103,36 @@ typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_ptr;
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4w_t;
 #define WG_OOB_OFF 0x80000000u
+// raw buffer of WG_OOB_OFF bytes from p on: a load at WG_OOB_OFF (or beyond) returns zeros
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_rsrc(const void* p) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)p, 0, (int)WG_OOB_OFF, 0x00020000);
+}
+
+// bf16 fragment (8 K values of this lane's channel) of a transposing read: rows k .. k + 3 at `lo`, k + 4 .. k + 7 at `hi`
+__device__ __forceinline__ bf16x8_t wg_read_tr16(const void* lo_p, const void* hi_p) {
+  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
+  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(lo_p));
+  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(hi_p));
+  const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+
+// (image, output row, output column) of output pixel p ...
+__device__ __forceinline__ void wg_pos_init(const WGArgs& a, int p, int& n, int& ho, int& wo) {
+  wo = p % a.Wo; const int t = p / a.Wo; ho = t % a.Ho; n = t / a.Ho;
+}
+// ... and the advance of a K-step's first pixel by the kp pixels of the step, where the steps stay inside one output row (Wo % kp == 0)
+__device__ __forceinline__ void wg_pos_step(const WGArgs& a, int kp, int& n, int& ho, int& wo) {
+  wo += kp;
+  if (wo >= a.Wo) { wo = 0; if (++ho == a.Ho) { ho = 0; ++n; } }
+}
+
+__device__ __forceinline__ void wg_zero(f32x16_t* acc, int n) {
+#pragma unroll
+  for (int i = 0; i < n; ++i)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+}
 
 // ROWSTEP: Wo % KP == 0, so every K-step (KP consecutive output pixels) lies inside ONE output row: image / row
 // / first column are workgroup-uniform scalars and each thread's byte offsets are loop constants (raw buffer
@@ -102,12 +156,8 @@ __global__ __launch_bounds__(256) void wg_kernel(const WGArgs a) {
   T* const smem = reinterpret_cast<T*>(wg_dsm);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware remap of the linear workgroup id: the 9 tap-workgroups (and channel tiles) of one pixel range become
-  // consecutive ids on ONE XCD, so the tiles they all re-read are served by that XCD's L2 instead of the fabric
-  // (measured: +15-35 % on layers with <= 72 tiles per pixel range, -5-12 % on the widest layers, hence the gate)
-  const unsigned lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-  const unsigned lin = gridDim.x <= 72 ? xcd_remap(lin0, gridDim.x * gridDim.y) : lin0;
-  const int bx = (int)(lin % gridDim.x), by = (int)(lin / gridDim.x);
+  int bx, by;
+  wg_decode_grid(blockIdx.y * gridDim.x + blockIdx.x, bx, by);
   const int ci_t = IM2COL ? 0 : bx % a.nci_t;
   const int tap = IM2COL ? 4 : (bx / a.nci_t) % 9;
   const int co_t = IM2COL ? bx : bx / (a.nci_t * 9);
@@ -126,7 +176,7 @@ __global__ __launch_bounds__(256) void wg_kernel(const WGArgs a) {
   constexpr int TPC = EPC / 2;          // taps per 16-B chunk of the im2col row
   unsigned imoff[IM2COL ? NX : 1][TPC];  // per-thread byte offsets of the chunk's taps (relative to pixel (ho-1, wo0-1))
   if constexpr (ROWSTEP) {
-    s_wo = pbeg % a.Wo; const int t = pbeg / a.Wo; s_ho = t % a.Ho; s_n = t / a.Ho;
+    wg_pos_init(a, pbeg, s_n, s_ho, s_wo);
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
       const int e = tid + 256 * i, row = e / CPRU, col = e % CPRU;
@@ -161,14 +211,13 @@ __global__ __launch_bounds__(256) void wg_kernel(const WGArgs a) {
     const bool row_ok = (unsigned)hi < (unsigned)a.H;
     const int wi0 = s_wo * a.stride + dc;
     const long long xb = ((long long)(s_n * a.H + hi) * a.W + wi0) * a.ldx;
-    __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc((void*)(U + ub), 0, (int)WG_OOB_OFF, 0x00020000);
-    __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)(X + xb), 0, (int)WG_OOB_OFF, 0x00020000);
+    __amdgpu_buffer_rsrc_t rU = wg_rsrc(U + ub), rX = wg_rsrc(X + xb);
 #pragma unroll
     for (int i = 0; i < NU; ++i) ru[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rU, uoffc[i], 0, 0));
     if constexpr (IM2COL) {
       // base = pixel (s_ho - 1, s_wo - 1) of image s_n; tap (r, s) of output pixel wo0+row is pixel (s_ho-1+r, s_wo-1+row+s)
       const long long xb2 = ((long long)(s_n * a.H + s_ho - 1) * a.W + s_wo - 1) * a.ldx;
-      __amdgpu_buffer_rsrc_t rI = __builtin_amdgcn_make_buffer_rsrc((void*)(X + xb2), 0, (int)WG_OOB_OFF, 0x00020000);
+      __amdgpu_buffer_rsrc_t rI = wg_rsrc(X + xb2);
 #pragma unroll
       for (int i = 0; i < NX; ++i) {
         const int col = (tid + 256 * i) % CPRX;
@@ -207,17 +256,14 @@ __global__ __launch_bounds__(256) void wg_kernel(const WGArgs a) {
   // tracked INCREMENTALLY (the K loop advances by KP pixels per step), so the loop has no integer division.
   int un[NU], uho[NU], uwo[NU];       // (image, ho, wo) of the adjoint rows (only needed for the shuffled layout)
   int xn[NX], xho[NX], xwo[NX];
-  auto init_pos = [&](int p, int& n, int& ho, int& wo) {
-    wo = p % a.Wo; const int t = p / a.Wo; ho = t % a.Ho; n = t / a.Ho;
-  };
-  auto advance_pos = [&](int& n, int& ho, int& wo) {
+  auto advance_pos = [&](int& n, int& ho, int& wo) {     // (any Wo: a step may cross several rows)
     wo += KP;
     while (wo >= a.Wo) { wo -= a.Wo; if (++ho == a.Ho) { ho = 0; ++n; } }
   };
 #pragma unroll
-  for (int i = 0; i < NU; ++i) init_pos(pbeg + (tid + 256 * i) / CPRU, un[i], uho[i], uwo[i]);
+  for (int i = 0; i < NU; ++i) wg_pos_init(a, pbeg + (tid + 256 * i) / CPRU, un[i], uho[i], uwo[i]);
 #pragma unroll
-  for (int i = 0; i < NX; ++i) init_pos(pbeg + (tid + 256 * i) / CPRX, xn[i], xho[i], xwo[i]);
+  for (int i = 0; i < NX; ++i) wg_pos_init(a, pbeg + (tid + 256 * i) / CPRX, xn[i], xho[i], xwo[i]);
   auto gload_gen = [&](int pb) {
 #pragma unroll
     for (int i = 0; i < NU; ++i) {
@@ -299,21 +345,13 @@ __global__ __launch_bounds__(256) void wg_kernel(const WGArgs a) {
         for (int f = 0; f < FA; ++f) {
           const int ch = wco * (BCO / 2) + 32 * f + 16 * grp16 + 4 * pp;
           const int k0 = kk * 16 + 8 * h + q;
-          s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(su + k0 * LDU + ch));
-          s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(su + (k0 + 4) * LDU + ch));
-          typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-          s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          fa[f] = __builtin_bit_cast(bf16x8_t, v);
+          fa[f] = wg_read_tr16(su + k0 * LDU + ch, su + (k0 + 4) * LDU + ch);
         }
 #pragma unroll
         for (int f = 0; f < FB; ++f) {
           const int ch = wci * (BCI / 2) + 32 * f + 16 * grp16 + 4 * pp;
           const int k0 = kk * 16 + 8 * h + q;
-          s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sx + k0 * LDX + ch));
-          s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sx + (k0 + 4) * LDX + ch));
-          typedef __attribute__((ext_vector_type(8))) short s16x8_t;
-          s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          fb[f] = __builtin_bit_cast(bf16x8_t, v);
+          fb[f] = wg_read_tr16(sx + k0 * LDX + ch, sx + (k0 + 4) * LDX + ch);
         }
 #pragma unroll
         for (int i = 0; i < FA; ++i)
@@ -374,17 +412,22 @@ extern "C" int dg_last_wgrad_kernel(void) { return g_last_wgrad; }
 // Split-K factor of a weight-gradient launch: ntiles x splits workgroups, the LARGEST count that still fits `target` (a whole
 // number of rounds of the chip's resident-workgroup slots, or the atomics budget `cap` if that is smaller).  Rounding the
 // split count up instead spilled a few workgroups into an extra, nearly empty round (96 tiles x 22 splits = 2112 = 4.125
-// rounds of 512 slots: -5 % against 1536 or 3072).  Returns the split count and the pixels per workgroup (multiple of 64).
-static int wg_pick_splits(int ntiles, long long target, long long cap, int Mpix, int* ppb) {
+// rounds of 512 slots: -5 % against 1536 or 3072).  A split gets at least min_ppb pixels; returns the split count and the pixels per
+// workgroup (a multiple of ppb_round).
+static int wg_pick_splits(int ntiles, long long target, long long cap, int Mpix, int min_ppb, int ppb_round, int* ppb) {
   if (cap < 512) cap = 512;
   if (target > cap) target = cap;
   int splits = (int)(target / ntiles);
-  const int max_splits = (Mpix + 255) / 256;
+  const int max_splits = (Mpix + min_ppb - 1) / min_ppb;
   if (splits > max_splits) splits = max_splits;
   if (splits < 1) splits = 1;
-  *ppb = ((Mpix + splits - 1) / splits + 63) / 64 * 64;
+  *ppb = ((Mpix + splits - 1) / splits + ppb_round - 1) / ppb_round * ppb_round;
   return (Mpix + *ppb - 1) / *ppb;
 }
+// Atomics budget of a launch: every workgroup ends with an atomic accumulate of its tile (tile_bytes; 64 KB for 128 x 128) at ~1.3 TB/s
+// chip-wide: cap the workgroup count so that this traffic stays below ~1/4 of the MFMA time (estimated at 600 TFLOP/s);
+// wg_pick_splits keeps >= 512 workgroups
+static long long wg_atomics_cap(double flops, double tile_bytes) { return (long long)(flops * 5.4e-4 / tile_bytes); }
 
 // Deterministic mode: plan `splits` copies of the launch's target region -- [dw | db] (Cout * 9 * Cin + Cout floats), or in dense-block
 // mode the span of the flat gradient buffer that holds the block's weight and bias gradients -- and return the split count granted.
@@ -427,6 +470,21 @@ static int wg_resident(K kernel, int lds_bytes) {
   return n;
 }
 
+// The split-K launch every launcher ends in: pick the split count, plan the copies of deterministic mode and re-pick when fewer are
+// granted, launch(splits) -- a.ppb is set by then --, reduce the copies.  target / cap / min_ppb / ppb_round: wg_pick_splits.
+template <typename Launch>
+static int wg_launch_splitk(WGArgs& a, hipStream_t st, int ntiles, long long target, long long cap, int min_ppb, int ppb_round,
+                            Launch launch) {
+  int splits = wg_pick_splits(ntiles, target, cap, a.Mpix, min_ppb, ppb_round, &a.ppb);
+  DetPlan plan; float* lo = nullptr; long long span = 0;
+  const int granted = wg_det_begin(a, splits, st, &plan, &lo, &span);
+  if (granted < 0) return DG_ERR_LAUNCH;
+  if (granted != splits) splits = wg_pick_splits(ntiles, (long long)ntiles * granted, 1ll << 40, a.Mpix, min_ppb, ppb_round, &a.ppb);
+  launch(splits);
+  if (dg_check_launch() != DG_OK) return DG_ERR_LAUNCH;
+  return wg_det_end(a, plan, lo, span, st);
+}
+
 template <typename T>
 static int wg_launch_im2col(WGArgs& a, hipStream_t st) {
   g_last_wgrad = WGK_IM2COL;
@@ -441,22 +499,13 @@ static int wg_launch_im2col(WGArgs& a, hipStream_t st) {
     occ = big_co ? wg_resident(wg_kernel<T, 128, 64, true, 32, true>, lds) : wg_resident(wg_kernel<T, 64, 64, true, 32, true>, lds);
     occ_cache[big_co].store(occ, std::memory_order_relaxed);
   }
-  // two whole rounds of the resident slots (2304 workgroups on 5 x 256 slots were 1.8 rounds)
-  int splits = 2 * 256 * occ / nco_t;
-  const int max_splits = (a.Mpix + 2047) / 2048;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  a.ppb = ((a.Mpix + splits - 1) / splits + 31) / 32 * 32;
-  splits = (a.Mpix + a.ppb - 1) / a.ppb;
-  DetPlan plan; float* lo = nullptr; long long span = 0;
-  const int granted = wg_det_begin(a, splits, st, &plan, &lo, &span);
-  if (granted < 0) return DG_ERR_LAUNCH;
-  if (granted != splits) { a.ppb = ((a.Mpix + granted - 1) / granted + 31) / 32 * 32; splits = (a.Mpix + a.ppb - 1) / a.ppb; }
-  dim3 grid(nco_t, splits);
-  if (big_co) hipLaunchKernelGGL((wg_kernel<T, 128, 64, true, 32, true>), grid, dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((wg_kernel<T, 64, 64, true, 32, true>), grid, dim3(256), lds, st, a);
-  if (dg_check_launch() != DG_OK) return DG_ERR_LAUNCH;
-  return wg_det_end(a, plan, lo, span, st);
+  // two whole rounds of the resident slots (2304 workgroups on 5 x 256 slots were 1.8 rounds), no atomics budget; unlike the other
+  // launchers: splits of >= 2048 pixels, in whole 32-pixel K-steps
+  return wg_launch_splitk(a, st, nco_t, 2ll * 256 * occ, 1ll << 40, 2048, 32, [&](int splits) {
+    const dim3 grid(nco_t, splits);
+    if (big_co) hipLaunchKernelGGL((wg_kernel<T, 128, 64, true, 32, true>), grid, dim3(256), lds, st, a);
+    else hipLaunchKernelGGL((wg_kernel<T, 64, 64, true, 32, true>), grid, dim3(256), lds, st, a);
+  });
 }
 
 template <typename T>
@@ -467,16 +516,13 @@ static int wg_launch(WGArgs& a, hipStream_t st) {
   const int nco_t = (a.Cout + bco - 1) / bco;
   a.nci_t = (a.Cin + bci - 1) / bci;
   const int ntiles = nco_t * 9 * a.nci_t;
-  // every workgroup ends with a 64-KB (tile) atomic accumulate at ~1.3 TB/s chip-wide: cap the workgroup count so
-  // that this traffic stays below ~1/4 of the MFMA time (estimated at 600 TFLOP/s), but keep >= 512 workgroups
   const double flops = 2.0 * 9 * a.Cin * (double)a.Cout * a.Mpix;
-  const long long cap = (long long)(flops * 5.4e-4 / (bco * bci * 4.0));
+  const long long cap = wg_atomics_cap(flops, bco * bci * 4.0);
   const bool rs = a.Wo % 32 == 0;
   // 64-pixel K-steps (half the barriers, half the resident workgroups) were measured equal to 32-pixel steps, and
   // 256x128 / 128x256 tiles (2 workgroups per CU, 25 % fewer staged bytes per flop) 8-20 % SLOWER than 128x128 with 3
   // workgroups per CU: neither is built.
   constexpr int PADE = sizeof(T) == 2 ? 32 : 0;
-  DetPlan plan; float* lo = nullptr; long long span = 0;
 #define WG_LAUNCH1(BCO, BCI, RS, KPV)                                                                 \
   do {                                                                                                \
     const int lds = 2 * KPV * (BCO + BCI + 2 * PADE) * (int)sizeof(T);                                \
@@ -486,12 +532,9 @@ static int wg_launch(WGArgs& a, hipStream_t st) {
     if (!occ) { occ = wg_resident(wg_kernel<T, BCO, BCI, RS, KPV>, lds); occ_cache.store(occ, std::memory_order_relaxed); } \
     /* 3 rounds of the resident slots, 2 when more than 3 workgroups share a CU */                    \
     const long long target = (long long)(occ > 3 ? 2 : 3) * 256 * occ;                                \
-    int splits = wg_pick_splits(ntiles, target, cap, a.Mpix, &a.ppb);                                 \
-    const int granted = wg_det_begin(a, splits, st, &plan, &lo, &span);                               \
-    if (granted < 0) return DG_ERR_LAUNCH;                                                            \
-    if (granted != splits) splits = wg_pick_splits(ntiles, (long long)ntiles * granted, 1ll << 40, a.Mpix, &a.ppb); \
-    dim3 grid(ntiles, splits);                                                                        \
-    hipLaunchKernelGGL((wg_kernel<T, BCO, BCI, RS, KPV>), grid, dim3(256), lds, st, a);               \
+    return wg_launch_splitk(a, st, ntiles, target, cap, 256, 64, [&](int splits) {                    \
+      hipLaunchKernelGGL((wg_kernel<T, BCO, BCI, RS, KPV>), dim3(ntiles, splits), dim3(256), lds, st, a); \
+    });                                                                                               \
   } while (0)
 #define WG_LAUNCH(BCO, BCI)                                                                           \
   do {                                                                                                \
@@ -504,8 +547,6 @@ static int wg_launch(WGArgs& a, hipStream_t st) {
   else WG_LAUNCH(64, 64);
 #undef WG_LAUNCH
 #undef WG_LAUNCH1
-  if (dg_check_launch() != DG_OK) return DG_ERR_LAUNCH;
-  return wg_det_end(a, plan, lo, span, st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -530,12 +571,9 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
   constexpr int BUF = KP * LDU + XR * LDX;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const unsigned lin0 = blockIdx.y * gridDim.x + blockIdx.x;
-  const unsigned lin = gridDim.x <= 72 ? xcd_remap(lin0, gridDim.x * gridDim.y) : lin0;
-  const int bx = (int)(lin % gridDim.x), by = (int)(lin / gridDim.x);
-  const int ci_t = bx % a.nci_t;
-  const int trow = (bx / a.nci_t) % 3;
-  const int co_t = bx / (a.nci_t * 3);
+  int bx, by, co_t, ci_t, trow;
+  wg_decode_grid(blockIdx.y * gridDim.x + blockIdx.x, bx, by);
+  wg_decode_tile(a, bx, co_t, ci_t, trow);
   const int co0 = co_t * BCO, ci0 = ci_t * BCI;
   const int dr = trow - 1;
   const int pbeg = by * a.ppb;
@@ -544,8 +582,8 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
   const T* __restrict__ U = reinterpret_cast<const T*>(a.u);
 
   uint4 ru[NU], rx[NX];
-  int s_wo = pbeg % a.Wo, s_ho, s_n;
-  { const int t = pbeg / a.Wo; s_ho = t % a.Ho; s_n = t / a.Ho; }
+  int s_n, s_ho, s_wo;
+  wg_pos_init(a, pbeg, s_n, s_ho, s_wo);
   unsigned uoffc[NU], xoffc[NX];
   int xrow[NX];
 #pragma unroll
@@ -574,8 +612,7 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
     const int wi0 = s_wo - 1;                                   // input column of tile row 0
     // the descriptor is based one pixel before the row segment; column -1 of the image gets an out-of-range offset
     const long long xb = ((long long)(s_n * a.H + (row_ok ? hi : 0)) * a.W + wi0) * a.ldx;
-    __amdgpu_buffer_rsrc_t rU = __builtin_amdgcn_make_buffer_rsrc((void*)(U + ub), 0, (int)WG_OOB_OFF, 0x00020000);
-    __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc((void*)(X + xb), 0, (int)WG_OOB_OFF, 0x00020000);
+    __amdgpu_buffer_rsrc_t rU = wg_rsrc(U + ub), rX = wg_rsrc(X + xb);
 #pragma unroll
     for (int i = 0; i < NU; ++i) ru[i] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rU, uoffc[i], 0, 0));
 #pragma unroll
@@ -603,14 +640,7 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
   };
 
   f32x16_t acc[3][FA][FB];
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int i = 0; i < FA; ++i)
-#pragma unroll
-      for (int j = 0; j < FB; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[s][i][j][e] = 0.f;
+  wg_zero(&acc[0][0][0], 3 * FA * FB);
 
   const int wci = wave;
   const int r32 = lane & 31, h = lane >> 5;
@@ -628,7 +658,6 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
     const T* sx = su + KP * LDU;
     if constexpr (sizeof(T) == 2) {
       const int grp16 = (lane >> 4) & 1, i16 = lane & 15, q = i16 >> 2, pp = i16 & 3;
-      typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 #pragma unroll
       for (int kk = 0; kk < KP / 16; ++kk) {
         bf16x8_t fa[FA];
@@ -636,10 +665,7 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
 #pragma unroll
         for (int f = 0; f < FA; ++f) {
           const int ch = 32 * f + 16 * grp16 + 4 * pp;
-          s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(su + k0 * LDU + ch));
-          s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(su + (k0 + 4) * LDU + ch));
-          s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-          fa[f] = __builtin_bit_cast(bf16x8_t, v);
+          fa[f] = wg_read_tr16(su + k0 * LDU + ch, su + (k0 + 4) * LDU + ch);
         }
 #pragma unroll
         for (int s = 0; s < 3; ++s) {
@@ -647,10 +673,7 @@ __global__ __launch_bounds__(256, 3) void wg3_kernel(const WGArgs a) {
 #pragma unroll
           for (int f = 0; f < FB; ++f) {
             const int ch = wci * (BCI / 4) + 32 * f + 16 * grp16 + 4 * pp;
-            s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sx + (k0 + s) * LDX + ch));
-            s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(sx + (k0 + s + 4) * LDX + ch));
-            s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            fb[f] = __builtin_bit_cast(bf16x8_t, v);
+            fb[f] = wg_read_tr16(sx + (k0 + s) * LDX + ch, sx + (k0 + s + 4) * LDX + ch);
           }
 #pragma unroll
           for (int i = 0; i < FA; ++i)
@@ -710,18 +733,42 @@ static int wg3_launch(WGArgs& a, hipStream_t st) {
   a.nci_t = (a.Cin + BCI - 1) / BCI;
   const int ntiles = nco_t * 3 * a.nci_t;
   const double flops = 2.0 * 9 * a.Cin * (double)a.Cout * a.Mpix;
-  const long long cap = (long long)(flops * 5.4e-4 / (3.0 * BCO * BCI * 4.0));     // same atomics-traffic budget as wg_launch
-  int splits = wg_pick_splits(ntiles, 2304, cap, a.Mpix, &a.ppb);                   // 3 rounds of 768 slots (3 per CU)
-  DetPlan plan; float* lo = nullptr; long long span = 0;
-  const int granted = wg_det_begin(a, splits, st, &plan, &lo, &span);
-  if (granted < 0) return DG_ERR_LAUNCH;
-  if (granted != splits) splits = wg_pick_splits(ntiles, (long long)ntiles * granted, 1ll << 40, a.Mpix, &a.ppb);
   constexpr int PADE = sizeof(T) == 2 ? 32 : 0;
   const int lds = 2 * (32 * (BCO + PADE) + 34 * (BCI + PADE)) * (int)sizeof(T);
   if (lds > 65536) DG_SET_MAX_LDS_ONCE((&wg3_kernel<T, BCO>), lds);
-  hipLaunchKernelGGL((wg3_kernel<T, BCO>), dim3(ntiles, splits), dim3(256), lds, st, a);
-  if (dg_check_launch() != DG_OK) return DG_ERR_LAUNCH;
-  return wg_det_end(a, plan, lo, span, st);
+  // 3 rounds of 768 slots (3 per CU)
+  return wg_launch_splitk(a, st, ntiles, 2304, wg_atomics_cap(flops, 3.0 * BCO * BCI * 4.0), 256, 64, [&](int splits) {
+    hipLaunchKernelGGL((wg3_kernel<T, BCO>), dim3(ntiles, splits), dim3(256), lds, st, a);
+  });
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Staging pieces of the two wide kernels (wg3w_kernel, wg3w_f8_kernel): tiles go global -> LDS by DMA, three buffers
+typedef int i32x4w_t __attribute__((ext_vector_type(4)));
+// raw buffer descriptor (in scalar registers) of WG_OOB_OFF bytes from `base` on
+__device__ __forceinline__ i32x4w_t wg_make_rs(const char* base) {
+  const unsigned long long b = (unsigned long long)base;
+  i32x4w_t rs;
+  rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  rs[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xffffu));
+  rs[2] = (int)WG_OOB_OFF;
+  rs[3] = 0x00020000;
+  return rs;
+}
+// global -> LDS DMA of 16 bytes per lane: the wave's 1024 bytes land linearly from LDS address m0v on; source = descriptor + lane
+// offset voff (+ a scalar offset soff)
+__device__ __forceinline__ void wg_dma(unsigned m0v, unsigned voff, const i32x4w_t& rs) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(m0v), "v"(voff), "s"(rs) : "memory");
+}
+__device__ __forceinline__ void wg_dma(unsigned m0v, unsigned voff, const i32x4w_t& rs, unsigned soff) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
+}
+// a wave has NXP + 2 or NXP + 3 pieces per tile in flight (NXP = 2, stride 2: 4): "at most NXP + 2 outstanding" = everything older
+// than the newest tile has landed
+__device__ __forceinline__ void wg_wait_older(bool newest_in_flight, bool s2) {
+  if (!newest_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  else if (s2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+  else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -745,16 +792,8 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bx, by;
   if (!wg_decode(a, bx, by)) return;
-  int ci_t = bx % a.nci_t;
-  int trow = (bx / a.nci_t) % 3;
-  int co_t = bx / (a.nci_t * 3);
-  if (a.tri) {                                  // bx = 3 * pair + tap row; pair p = t (t + 1) / 2 + input tile, input tile <= t
-    trow = bx % 3;
-    const int p = bx / 3;
-    co_t = 0;
-    while ((co_t + 1) * (co_t + 2) / 2 <= p) ++co_t;
-    ci_t = p - co_t * (co_t + 1) / 2;
-  }
+  int co_t, ci_t, trow;
+  wg_decode_tile_wide(a, bx, co_t, ci_t, trow);
   const int co0 = co_t * BCO, ci0 = ci_t * BCI;
   const int dr = trow - 1;
   const int pbeg = by * a.ppb;
@@ -788,21 +827,8 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
     xoff[j] = (row < XROWS && ci < a.Cin) ? (unsigned)(((long long)row * a.ldx + ci) * 2) : WG_OOB_OFF;
   }
   const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)wgw_dsm));
-  typedef int i32x4w_t __attribute__((ext_vector_type(4)));
-  auto dma = [&](unsigned m0v, unsigned voff, const i32x4w_t& rs) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(m0v), "v"(voff), "s"(rs) : "memory");
-  };
-  auto make_rs = [&](const char* base) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4w_t rs;
-    rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    rs[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xffffu));
-    rs[2] = (int)WG_OOB_OFF;
-    rs[3] = 0x00020000;
-    return rs;
-  };
-  int s_wo = pbeg % a.Wo, s_ho, s_n;
-  { const int t = pbeg / a.Wo; s_ho = t % a.Ho; s_n = t / a.Ho; }
+  int s_n, s_ho, s_wo;
+  wg_pos_init(a, pbeg, s_n, s_ho, s_wo);
   // tile t (32 output pixels of one row + the 34 input pixels under them) -> buffer buf
   auto issue = [&](int buf, int t) {
     const long long ub = !a.u_ps ? ((long long)(s_n * a.Ho + s_ho) * a.Wo + s_wo) * a.ldu
@@ -811,30 +837,24 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
     const bool row_ok = (unsigned)hi < (unsigned)a.H;
     const int wi0 = (S2 ? 2 * s_wo : s_wo) - 1;                 // input column of tile row 0
     const long long xb = ((long long)(s_n * a.H + (row_ok ? hi : 0)) * a.W + wi0) * a.ldx;
-    const i32x4w_t rsU = make_rs(U + ub * 2), rsX = make_rs(X + xb * 2);
+    const i32x4w_t rsU = wg_make_rs(U + ub * 2), rsX = wg_make_rs(X + xb * 2);
     const unsigned m0b = lds0 + (unsigned)buf * BUFB;
-    dma(m0b + (unsigned)wave * 1024u, uoff[0], rsU);
-    dma(m0b + (unsigned)(wave + 4) * 1024u, uoff[1], rsU);
+    wg_dma(m0b + (unsigned)wave * 1024u, uoff[0], rsU);
+    wg_dma(m0b + (unsigned)(wave + 4) * 1024u, uoff[1], rsU);
 #pragma unroll
     for (int j = 0; j < NXP; ++j) {
       const unsigned vo = (row_ok && (unsigned)(wi0 + xr[j]) < (unsigned)a.W) ? xoff[j] : WG_OOB_OFF;
-      dma(m0b + SU_B + (unsigned)(wave + 4 * j) * 1024u, vo, rsX);
+      wg_dma(m0b + SU_B + (unsigned)(wave + 4 * j) * 1024u, vo, rsX);
     }
     if ((t & 3) == wave) {                                      // the last rows (+ zero rows): one wave per step, in turn
       const unsigned vo = (row_ok && (unsigned)(wi0 + xr[NXP]) < (unsigned)a.W) ? xoff[NXP] : WG_OOB_OFF;
-      dma(m0b + SU_B + (unsigned)LASTP * 1024u, vo, rsX);
+      wg_dma(m0b + SU_B + (unsigned)LASTP * 1024u, vo, rsX);
     }
-    s_wo += KP;
-    if (s_wo >= a.Wo) { s_wo = 0; if (++s_ho == a.Ho) { s_ho = 0; ++s_n; } }
+    wg_pos_step(a, KP, s_n, s_ho, s_wo);
   };
 
   f32x16_t acc[3][4];
-#pragma unroll
-  for (int s = 0; s < 3; ++s)
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[s][f][e] = 0.f;
+  wg_zero(&acc[0][0], 12);
 
   // fragment read offsets (bytes inside a buffer): row 8h + q (+ tap), 64-B group XOR (row & 3), 32 * grp16 + 8 * pp inside
   const int h = lane >> 5, grp16 = (lane >> 4) & 1, i16 = lane & 15, q = i16 >> 2, pp = i16 & 3, r32 = lane & 31;
@@ -862,17 +882,9 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
 
   issue(0, 0);
   if (nsteps > 1) issue(1, 1);
-  // a wave has NXP + 2 or NXP + 3 pieces per tile in flight: "at most NXP + 2 outstanding" = everything older than the
-  // newest tile has landed
-  auto wait_older = [&](bool newest_in_flight) {
-    if (!newest_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (S2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  };
-  wait_older(nsteps > 1);
+  wg_wait_older(nsteps > 1, S2);
   __syncthreads();
   int cur = 0;
-  typedef __attribute__((ext_vector_type(8))) short s16x8_t;
   for (int ks = 0; ks < nsteps; ++ks) {
     const bool ahead = ks + 2 < nsteps;
     int nb = cur + 2; if (nb >= 3) nb -= 3;
@@ -884,10 +896,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
     // of tap s+1 runs under the four MFMAs of tap s instead of in front of its own
     auto read_fb = [&](int s, int kk) {
       const unsigned char* pb = sb + bxs[s] + kk * 16 * XK * ROWB;
-      const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pb));
-      const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pb + 4 * XK * ROWB));
-      const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      return __builtin_bit_cast(bf16x8_t, v);
+      return wg_read_tr16(pb, pb + 4 * XK * ROWB);
     };
     bf16x8_t fb = read_fb(0, 0);
 #pragma unroll
@@ -896,10 +905,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         const unsigned char* pa = sb + (bu ^ (f << 6)) + kk * 16 * ROWB;
-        const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pa));
-        const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pa + 4 * ROWB));
-        const s16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        fa[f] = __builtin_bit_cast(bf16x8_t, v);
+        fa[f] = wg_read_tr16(pa, pa + 4 * ROWB);
       }
       if (db_now) {
 #pragma unroll
@@ -924,7 +930,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
         fb = fbn;
       }
     }
-    wait_older(ahead);
+    wg_wait_older(ahead, S2);
     __syncthreads();
     if (++cur == 3) cur = 0;
   }
@@ -952,27 +958,28 @@ __global__ __launch_bounds__(256, 2) void wg3w_kernel(const WGArgs a) {
   }
 }
 
-template <bool S2>
-static int wg3w_launch(WGArgs& a, hipStream_t st) {
-  g_last_wgrad = a.tri ? WGK_DENSE : S2 ? WGK_WIDE_S2 : WGK_WIDE_S1;
+// Launch of a wide kernel (bf16 or fp8; a.nci_t set) on its (adjoint tile, input tile, tap row) tiles, in grouped order where
+// wg_group_order takes it; launch(grid) starts the kernel
+template <typename Launch>
+static int wg_wide_launch(WGArgs& a, hipStream_t st, int nco_t, Launch launch) {
   constexpr int BCO = 128, BCI = 128;
-  const int nco_t = (a.Cout + BCO - 1) / BCO;
-  a.nci_t = (a.Cin + BCI - 1) / BCI;
   const int npairs = a.tri ? nco_t * (nco_t + 1) / 2 : nco_t * a.nci_t;            // dense-block mode: input tile <= adjoint tile
   const int ntiles = 3 * npairs;
   const double flops = 2.0 * 9 * BCO * (double)BCI * npairs * a.Mpix;
-  const long long cap = (long long)(flops * 5.4e-4 / (3.0 * BCO * BCI * 4.0));     // same atomics-traffic budget as wg_launch
-  int splits = wg_pick_splits(ntiles, 1536, cap, a.Mpix, &a.ppb);                   // 3 rounds of 512 slots (2 per CU)
-  DetPlan plan; float* lo = nullptr; long long span = 0;
-  const int granted = wg_det_begin(a, splits, st, &plan, &lo, &span);
-  if (granted < 0) return DG_ERR_LAUNCH;
-  if (granted != splits) splits = wg_pick_splits(ntiles, (long long)ntiles * granted, 1ll << 40, a.Mpix, &a.ppb);
+  // 3 rounds of 512 slots (2 per CU)
+  return wg_launch_splitk(a, st, ntiles, 1536, wg_atomics_cap(flops, 3.0 * BCO * BCI * 4.0), 256, 64, [&](int splits) {
+    wg_group_order(a, nco_t, ntiles, splits);
+    launch(a.grp ? dim3(wg_group_blocks(a)) : dim3(ntiles, splits));
+  });
+}
+
+template <bool S2>
+static int wg3w_launch(WGArgs& a, hipStream_t st) {
+  g_last_wgrad = a.tri ? WGK_DENSE : S2 ? WGK_WIDE_S2 : WGK_WIDE_S1;
+  a.nci_t = (a.Cin + 127) / 128;
   constexpr int lds = 3 * (32 * 256 + (S2 ? 68 : 36) * 256);
   if (lds > 65536) DG_SET_MAX_LDS_ONCE((&wg3w_kernel<S2>), lds);
-  wg_group_order(a, nco_t, ntiles, splits);
-  hipLaunchKernelGGL((wg3w_kernel<S2>), a.grp ? dim3(wg_group_blocks(a)) : dim3(ntiles, splits), dim3(256), lds, st, a);
-  if (dg_check_launch() != DG_OK) return DG_ERR_LAUNCH;
-  return wg_det_end(a, plan, lo, span, st);
+  return wg_wide_launch(a, st, (a.Cout + 127) / 128, [&](dim3 grid) { hipLaunchKernelGGL((wg3w_kernel<S2>), grid, dim3(256), lds, st, a); });
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -1008,14 +1015,8 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   int bx, by;
   if (!wg_decode(a, bx, by)) return;
-  int ci_t = bx % a.nci_t, trow = (bx / a.nci_t) % 3, co_t = bx / (a.nci_t * 3);
-  if (a.tri) {                                  // dense-block mode as in wg3w_kernel: bx = 3 * pair + tap row, input tile <= adjoint tile
-    trow = bx % 3;
-    const int p = bx / 3;
-    co_t = 0;
-    while ((co_t + 1) * (co_t + 2) / 2 <= p) ++co_t;
-    ci_t = p - co_t * (co_t + 1) / 2;
-  }
+  int co_t, ci_t, trow;
+  wg_decode_tile_wide(a, bx, co_t, ci_t, trow);
   const int co0 = co_t * BCO, ci0 = ci_t * BCI;
   const int dr = trow - 1;
   const int pbeg = by * a.ppb;
@@ -1033,21 +1034,8 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
   const int lchunk = ((((pchunk >> 1) ^ ((drow >> 1) & 3)) << 1) | (pchunk & 1)) * 16;          // byte offset inside the 128-byte row
   const unsigned ulane = (unsigned)(drow * (int)a.ldu + lchunk), xlane = (unsigned)(drow * (int)a.ldx + lchunk);
   const unsigned lds0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long long)((__attribute__((address_space(3))) unsigned char*)wg8_dsm));
-  typedef int i32x4w_t __attribute__((ext_vector_type(4)));
-  auto dma = [&](unsigned m0v, unsigned voff, const i32x4w_t& rs, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(m0v), "v"(voff), "s"(rs), "s"(soff) : "memory");
-  };
-  auto make_rs = [&](const char* base) {
-    const unsigned long long b = (unsigned long long)base;
-    i32x4w_t rs;
-    rs[0] = __builtin_amdgcn_readfirstlane((int)(unsigned)b);
-    rs[1] = __builtin_amdgcn_readfirstlane((int)((unsigned)(b >> 32) & 0xffffu));
-    rs[2] = (int)WG_OOB_OFF;
-    rs[3] = 0x00020000;
-    return rs;
-  };
-  int s_wo = pbeg % a.Wo, s_ho, s_n;
-  { const int t = pbeg / a.Wo; s_ho = t % a.Ho; s_n = t / a.Ho; }
+  int s_n, s_ho, s_wo;
+  wg_pos_init(a, pbeg, s_n, s_ho, s_wo);
   // tile t (64 output pixels of one row + the input pixels under them) -> buffer buf.  A lane whose input pixel lies outside
   // the image gets the out-of-range offset (the range check looks at the lane offset only: the load returns zeros).
   auto issue = [&](int buf, int t) {
@@ -1056,23 +1044,22 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
     const bool row_ok = (unsigned)hi < (unsigned)a.H;
     const int wi0 = XK * s_wo - 1;                              // input column of tile row 0
     const long long xb = ((long long)(s_n * a.H + (row_ok ? hi : 0)) * a.W + wi0) * a.ldx + ci0;
-    const i32x4w_t rsU = make_rs(U + ub), rsX = make_rs(X + xb);
+    const i32x4w_t rsU = wg_make_rs(U + ub), rsX = wg_make_rs(X + xb);
     const unsigned m0b = lds0 + (unsigned)buf * BUFB;
 #pragma unroll
-    for (int j = 0; j < 2; ++j) dma(m0b + (unsigned)(wave + 4 * j) * 1024u, ulane, rsU, (unsigned)((wave + 4 * j) * 8 * (int)a.ldu));
+    for (int j = 0; j < 2; ++j) wg_dma(m0b + (unsigned)(wave + 4 * j) * 1024u, ulane, rsU, (unsigned)((wave + 4 * j) * 8 * (int)a.ldu));
 #pragma unroll
     for (int j = 0; j < NXW; ++j) {
       const int row0 = 8 * (wave + 4 * j);
       const unsigned vo = (row_ok && (unsigned)(wi0 + row0 + drow) < (unsigned)a.W) ? xlane : WG_OOB_OFF;
-      dma(m0b + SU_B + (unsigned)(wave + 4 * j) * (unsigned)XPITCH, vo, rsX, (unsigned)(row0 * (int)a.ldx));
+      wg_dma(m0b + SU_B + (unsigned)(wave + 4 * j) * (unsigned)XPITCH, vo, rsX, (unsigned)(row0 * (int)a.ldx));
     }
     if ((t & 3) == wave) {                                      // the last piece (2 / 1 of its rows are read): one wave per step, in turn
       constexpr int R0 = 8 * (XPIECES - 1);
       const unsigned vo = (row_ok && drow < XROWS - R0 && (unsigned)(wi0 + R0 + drow) < (unsigned)a.W) ? xlane : WG_OOB_OFF;
-      dma(m0b + SU_B + (unsigned)(XPIECES - 1) * (unsigned)XPITCH, vo, rsX, (unsigned)(R0 * (int)a.ldx));
+      wg_dma(m0b + SU_B + (unsigned)(XPIECES - 1) * (unsigned)XPITCH, vo, rsX, (unsigned)(R0 * (int)a.ldx));
     }
-    s_wo += KP;
-    if (s_wo >= a.Wo) { s_wo = 0; if (++s_ho == a.Ho) { s_ho = 0; ++s_n; } }
+    wg_pos_step(a, KP, s_n, s_ho, s_wo);
   };
 
   f32x16_t acc[3][4];
@@ -1100,12 +1087,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
 
   issue(0, 0);
   if (nsteps > 1) issue(1, 1);
-  auto wait_older = [&](bool newest_in_flight) {        // a tile = NXW + 2 or NXW + 3 pieces per wave: everything older than the newest has landed
-    if (!newest_in_flight) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (S2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  };
-  wait_older(nsteps > 1);
+  wg_wait_older(nsteps > 1, S2);
   __syncthreads();
   int cur = 0;
   for (int ks = 0; ks < nsteps; ++ks) {
@@ -1140,7 +1122,7 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
       asm volatile("" : "+v"(acc[0][f]), "+v"(acc[1][f]), "+v"(acc[2][f]) :: "memory");
       __builtin_amdgcn_sched_barrier(0);
     }
-    wait_older(ahead);
+    wg_wait_older(ahead, S2);
     __syncthreads();
     if (++cur == 3) cur = 0;
   }
@@ -1169,30 +1151,33 @@ __global__ __launch_bounds__(256, 2) void wg3w_f8_kernel(const WGArgs a) {
 // launch of the fp8 kernel for a prepared WGArgs (x / u / ex / eu / geometry / Mpix set; tri + dwk[] in dense-block mode)
 static int wg3w_f8_launch(WGArgs& a, hipStream_t st) {
   g_last_wgrad = WGK_F8;
-  constexpr int BCO = 128, BCI = 128;
-  const int nco_t = a.Cout / BCO;
-  a.nci_t = a.Cin / BCI;
-  const int npairs = a.tri ? nco_t * (nco_t + 1) / 2 : nco_t * a.nci_t;
-  const int ntiles = 3 * npairs;
-  const double flops = 2.0 * 9 * BCO * (double)BCI * npairs * a.Mpix;
-  const long long cap = (long long)(flops * 5.4e-4 / (3.0 * BCO * BCI * 4.0));     // the atomics-traffic budget of the bf16 launchers
-  int splits = wg_pick_splits(ntiles, 1536, cap, a.Mpix, &a.ppb);                   // 3 rounds of 512 slots (2 per CU)
-  DetPlan plan; float* lo = nullptr; long long span = 0;
-  const int granted = wg_det_begin(a, splits, st, &plan, &lo, &span);
-  if (granted < 0) return DG_ERR_LAUNCH;
-  if (granted != splits) splits = wg_pick_splits(ntiles, (long long)ntiles * granted, 1ll << 40, a.Mpix, &a.ppb);
-  wg_group_order(a, nco_t, ntiles, splits);
-  const dim3 grid = a.grp ? dim3(wg_group_blocks(a)) : dim3(ntiles, splits);
+  a.nci_t = a.Cin / 128;
   if (a.stride == 2) {
     constexpr int lds2 = 3 * (64 * 128 + 17 * 1152);
     DG_SET_MAX_LDS_ONCE((&wg3w_f8_kernel<true>), lds2);
-    hipLaunchKernelGGL(wg3w_f8_kernel<true>, grid, dim3(256), lds2, st, a);
-  } else {
-    constexpr int lds = 3 * (64 * 128 + 9 * 1024);
-    hipLaunchKernelGGL(wg3w_f8_kernel<false>, grid, dim3(256), lds, st, a);
+    return wg_wide_launch(a, st, a.Cout / 128, [&](dim3 grid) { hipLaunchKernelGGL(wg3w_f8_kernel<true>, grid, dim3(256), lds2, st, a); });
   }
-  if (dg_check_launch() != DG_OK) return DG_ERR_LAUNCH;
-  return wg_det_end(a, plan, lo, span, st);
+  constexpr int lds = 3 * (64 * 128 + 9 * 1024);
+  return wg_wide_launch(a, st, a.Cout / 128, [&](dim3 grid) { hipLaunchKernelGGL(wg3w_f8_kernel<false>, grid, dim3(256), lds, st, a); });
+}
+
+// WGArgs of an entry point from its validated geometry (epc = elements per 16-byte chunk of the adjoint); DG_ERR_BAD_SHAPE when the
+// pixel count does not fit an int
+static int wg_args_init(WGArgs& a, const dg_conv_geom* g, const void* x, const void* u, float* dw, int epc) {
+  a.x = x; a.u = u; a.dw = dw; a.ldx = g->ldx; a.ldu = g->ldy;
+  a.H = g->H; a.W = g->W; a.stride = g->stride; a.Ho = g->H / g->stride; a.Wo = g->W / g->stride;
+  a.Cin = g->Cin; a.Cout = g->Cout;
+  a.u_ps = g->pixel_shuffle; a.cps_chunks = g->pixel_shuffle ? g->Cout / 4 / epc : 1;
+  const long long mp = (long long)g->N * a.Ho * a.Wo;
+  if (mp >= (1ll << 31)) return DG_ERR_BAD_SHAPE;
+  a.Mpix = (int)mp;
+  return DG_OK;
+}
+// ... of the fp8 entry points: the block exponents, and a row of W + 8 pixels within the 2^31 bytes a lane offset reaches
+static int wg_args_init_f8(WGArgs& a, const dg_conv_geom* g, const void* xq, const void* ex, const void* dyq, const void* ey, float* dw) {
+  if (wg_args_init(a, g, xq, dyq, dw, 16) != DG_OK || (long long)(a.W + 8) * a.ldx >= (1ll << 31)) return DG_ERR_BAD_SHAPE;
+  a.ex = (const unsigned char*)ex; a.eu = (const unsigned char*)ey;
+  return DG_OK;
 }
 
 // dw[co][tap][ci] (fp32, accumulated into) += sum_p dy[p, co] * x[src(p, tap), ci] for E4M3 operands with per-32-channel-block
@@ -1207,13 +1192,7 @@ extern "C" int dg_conv3x3_wgrad_f8(const dg_conv_geom* g, const void* xq, const 
   if (g->Cin <= 0 || g->Cout <= 0 || g->Cin % 128 || g->Cout % 128 || (g->W / g->stride) % 64) return DG_ERR_BAD_SHAPE;
   if (g->ldx < g->Cin || g->ldy < g->Cout || g->ldx % 16 || g->ldy % 16) return DG_ERR_BAD_SHAPE;
   WGArgs a{};
-  a.x = xq; a.u = dyq; a.dw = dw; a.ldx = g->ldx; a.ldu = g->ldy;
-  a.ex = (const unsigned char*)ex; a.eu = (const unsigned char*)ey;
-  a.H = g->H; a.W = g->W; a.stride = g->stride; a.Ho = g->H / g->stride; a.Wo = g->W / g->stride;
-  a.Cin = g->Cin; a.Cout = g->Cout; a.u_ps = 0; a.cps_chunks = 1;
-  const long long mp = (long long)g->N * a.Ho * a.Wo;
-  if (mp >= (1ll << 31) || (long long)(a.W + 8) * a.ldx >= (1ll << 31)) return DG_ERR_BAD_SHAPE;
-  a.Mpix = (int)mp;
+  if (wg_args_init_f8(a, g, xq, ex, dyq, ey, dw) != DG_OK) return DG_ERR_BAD_SHAPE;
   return wg3w_f8_launch(a, reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -1230,20 +1209,18 @@ extern "C" int dg_conv3x3_wgrad_dense_f8(const dg_conv_geom* g, int nconv, const
   for (int k = 0; k < nconv; ++k)
     if (!dw[k]) return DG_ERR_BAD_ARG;
   WGArgs a{};
-  a.x = xq; a.u = dyq; a.dw = dw[0]; a.ldx = g->ldx; a.ldu = g->ldy;
-  a.ex = (const unsigned char*)ex; a.eu = (const unsigned char*)ey;
-  a.H = g->H; a.W = g->W; a.stride = 1; a.Ho = g->H; a.Wo = g->W;
-  a.Cin = g->Cin; a.Cout = g->Cout; a.u_ps = 0; a.cps_chunks = 1;
-  const long long mp = (long long)g->N * a.Ho * a.Wo;
-  if (mp >= (1ll << 31) || (long long)(a.W + 8) * a.ldx >= (1ll << 31)) return DG_ERR_BAD_SHAPE;
-  a.Mpix = (int)mp;
+  if (wg_args_init_f8(a, g, xq, ex, dyq, ey, dw[0]) != DG_OK) return DG_ERR_BAD_SHAPE;
   a.tri = 1;
   for (int k = 0; k < nconv; ++k) { a.dwk[k] = dw[k]; a.dbk[k] = nullptr; }
   return wg3w_f8_launch(a, reinterpret_cast<hipStream_t>(stream));
 }
 
-extern "C" int dg_colsum(int dtype, const void* dy, int64_t rows_outer, int64_t ld_outer, int64_t rows_inner, int64_t ld, int C,
-                         float* db, void* stream);
+// The im2col kernel's shapes: <= 2 real input channels, stride 1, rows of whole 32-pixel K-steps (DG_WG_NOIM2COL, read once, turns
+// the kernel off)
+static bool wg_im2col_shape(const dg_conv_geom* g) {
+  static const bool no_im2col = getenv("DG_WG_NOIM2COL") != nullptr;
+  return !no_im2col && g->cin_real > 0 && g->cin_real <= 2 && g->stride == 1 && !g->pixel_shuffle && (g->W / g->stride) % 32 == 0;
+}
 
 extern "C" int dg_conv3x3_wgrad(const dg_conv_geom* g, const void* x, const void* dy, float* dw, float* db, void* stream) {
   g_last_wgrad = WGK_NONE;
@@ -1254,40 +1231,28 @@ extern "C" int dg_conv3x3_wgrad(const dg_conv_geom* g, const void* x, const void
   if (g->Cin % 8 || g->Cout % 16 || g->Cin <= 0 || g->Cout <= 0) return DG_ERR_BAD_SHAPE;
   if (g->pixel_shuffle && (g->stride != 1 || (g->Cout / 4) % 16)) return DG_ERR_BAD_SHAPE;
   const int epc = g->dtype == DG_F32 ? 4 : 8;
-  // the im2col kernel (<= 2 real input channels) gathers single (channel 0, channel 1) pairs, so its x may be the COMPACT
-  // tensor [N, H, W, 2] (ldx = 2); every other kernel reads whole 16-byte channel chunks
-  const bool im2col_shape = g->cin_real > 0 && g->cin_real <= 2 && g->stride == 1 && !g->pixel_shuffle && (g->W / g->stride) % 32 == 0 &&
-                            getenv("DG_WG_NOIM2COL") == nullptr;
-  if ((im2col_shape ? (g->ldx % 2 || g->ldx < 2) : (g->ldx % epc != 0)) || g->ldy % epc) return DG_ERR_BAD_SHAPE;
+  // the im2col kernel gathers single (channel 0, channel 1) pairs, so its x may be the COMPACT tensor [N, H, W, 2] (ldx = 2); every
+  // other kernel reads whole 16-byte channel chunks
+  const bool im2col = wg_im2col_shape(g);
+  if ((im2col ? (g->ldx % 2 || g->ldx < 2) : (g->ldx % epc != 0)) || g->ldy % epc) return DG_ERR_BAD_SHAPE;
   WGArgs a{};
-  a.x = x; a.u = dy; a.dw = dw; a.ldx = g->ldx; a.ldu = g->ldy;
-  a.H = g->H; a.W = g->W; a.stride = g->stride; a.Ho = g->H / g->stride; a.Wo = g->W / g->stride;
-  a.Cin = g->Cin; a.Cout = g->Cout;
-  a.u_ps = g->pixel_shuffle; a.cps_chunks = g->pixel_shuffle ? g->Cout / 4 / epc : 1;
-  const long long mp = (long long)g->N * a.Ho * a.Wo;
-  if (mp >= (1ll << 31)) return DG_ERR_BAD_SHAPE;
-  a.Mpix = (int)mp;
+  if (wg_args_init(a, g, x, dy, dw, epc) != DG_OK) return DG_ERR_BAD_SHAPE;
   a.db = db;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  static const bool no_im2col = getenv("DG_WG_NOIM2COL") != nullptr;
-  if (!no_im2col && g->cin_real > 0 && g->cin_real <= 2 && g->stride == 1 && !g->pixel_shuffle && a.Wo % 32 == 0)
-    return g->dtype == DG_F32 ? wg_launch_im2col<float>(a, st) : wg_launch_im2col<bf16_t>(a, st);
+  if (im2col) return g->dtype == DG_F32 ? wg_launch_im2col<float>(a, st) : wg_launch_im2col<bf16_t>(a, st);
   // narrow row-of-taps kernel (wg3) against the per-tap kernel: +4-10 % with >= 2 input-channel tiles or multi-megapixel
   // batches, -20 % on the 128-channel 128^2 layers; the wide kernel (wg3w) takes every layer it is eligible for
-  constexpr bool no_rows = false, no_wide = false, no_wide_s2 = false;
   const bool wide = g->dtype == DG_BF16 && a.Cout >= 128 && a.Cin >= 128;
   // (the -20 % of the row-of-taps shape on 128-channel 128^2 layers was the narrow wg3 kernel with the old split rounding: the
   // wide kernel is +19-37 % there too)
-  const bool rows = !no_rows && g->stride == 1 && a.Wo % 32 == 0 && a.Cout >= 64 &&
-                    (a.Cin >= 256 || (a.Cin >= 64 && a.Mpix >= (1 << 22)) || (wide && !no_wide));
-  const bool wide_s1 = rows && wide && !no_wide;
+  const bool rows = g->stride == 1 && a.Wo % 32 == 0 && a.Cout >= 64 && (a.Cin >= 256 || (a.Cin >= 64 && a.Mpix >= (1 << 22)) || wide);
+  const bool wide_s1 = rows && wide;
   // stride 2 on the wide kernel (x tile of 65 input pixels per 32 output pixels)
-  const bool wide_s2 = !no_rows && !no_wide_s2 && wide && g->stride == 2 && a.Wo % 32 == 0 && !g->pixel_shuffle;
-  constexpr bool no_fused_db = false;
-  const bool fused_db = db && (wide_s1 || wide_s2) && !g->pixel_shuffle && !no_fused_db;   // the wide kernel sums the adjoint itself
+  const bool wide_s2 = wide && g->stride == 2 && a.Wo % 32 == 0 && !g->pixel_shuffle;
+  const bool fused_db = db && (wide_s1 || wide_s2) && !g->pixel_shuffle;   // the wide kernel sums the adjoint itself
   if (db && !fused_db) {   // bias gradient as a separate column-sum pass over the adjoint
     if (g->pixel_shuffle) return DG_ERR_BAD_ARG;
-    int rc = dg_colsum(g->dtype, dy, mp, g->ldy, 1, g->ldy, g->Cout, db, stream);
+    int rc = dg_colsum(g->dtype, dy, a.Mpix, g->ldy, 1, g->ldy, g->Cout, db, stream);
     if (rc) return rc;
   }
   a.db = fused_db ? db : nullptr;
@@ -1313,14 +1278,7 @@ extern "C" int dg_conv3x3_wgrad_dense(const dg_conv_geom* g, int nconv, const vo
   for (int k = 0; k < nconv; ++k)
     if (!dw[k]) return DG_ERR_BAD_ARG;
   WGArgs a{};
-  a.x = x; a.u = dy; a.dw = dw[0]; a.ldx = g->ldx; a.ldu = g->ldy;
-  a.H = g->H; a.W = g->W; a.stride = 1; a.Ho = g->H; a.Wo = g->W;
-  a.Cin = g->Cin; a.Cout = g->Cout;
-  a.u_ps = 0; a.cps_chunks = 1;
-  const long long mp = (long long)g->N * a.Ho * a.Wo;
-  if (mp >= (1ll << 31)) return DG_ERR_BAD_SHAPE;
-  a.Mpix = (int)mp;
-  a.db = nullptr;
+  if (wg_args_init(a, g, x, dy, dw[0], 8) != DG_OK) return DG_ERR_BAD_SHAPE;
   a.tri = 1;
   for (int k = 0; k < nconv; ++k) { a.dwk[k] = dw[k]; a.dbk[k] = db ? db[k] : nullptr; }
   return wg3w_launch<false>(a, reinterpret_cast<hipStream_t>(stream));

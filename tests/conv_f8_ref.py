@@ -538,6 +538,8 @@ WCASES = [
     F8WCase("f8-wgrad-256-384-5x64-sliced", "wgrad", (2, 5, 64, 256, 384, 1), sliced=True),
     F8WCase("f8-wgrad-s2-128-256-wo64", "wgrad", (2, 8, 128, 128, 256, 2)),
     F8WCase("f8-wgrad-s2-256-128-wo128", "wgrad", (1, 6, 256, 256, 128, 2)),
+    # 96 tiles per pixel range (> 72): the grouped launch order, 2 splits x 2 units of 48 tiles in 8 unit slots, half of the workgroups padding
+    F8WCase("f8-wgrad-512-1024-8x64", "wgrad", (1, 8, 64, 512, 1024, 1)),
     F8WCase("f8-wgrad-dense-1", "dense", (1, 4, 64, 1)),
     F8WCase("f8-wgrad-dense-3", "dense", (2, 3, 64, 3)),
     F8WCase("f8-wgrad-dense-5", "dense", (1, 4, 128, 5)),

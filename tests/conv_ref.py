@@ -694,6 +694,8 @@ CASES += [
     _wg("wgrad-wide-128-128-8x32", (1, 8, 32, 128, 128, 1, 0), W1, db=BOTH),
     _wg("wgrad-wide-320-192-16x64", (1, 16, 64, 320, 192, 1, 0), W1R, db=BOTH),
     _wg("wgrad-wide-256-256ps-8x32", (1, 8, 32, 256, 256, 1, 1), W1R, db=(False,)),
+    # ... 96 tiles per pixel range (> 72): the grouped launch order, 2 splits x 2 units of 48 tiles in 8 unit slots, half of the workgroups padding
+    _wg("wgrad-wide-512-1024-8x64", (1, 8, 64, 512, 1024, 1, 0), W1R, db=(True,)),
 ]
 # wide kernel, stride 2: Wo 32 and 64, two images
 for _ci, _co in ((128, 128), (320, 192)):
