@@ -1,5 +1,7 @@
 """EOF analysis on the MI355X (csrc/eof.hip): kernels against float64 numpy on ragged shapes in every input layout, the fit
-against sklearn and the reference (tests/golden/eof.json), determinism, and a full-size fit from the resident feed."""
+against sklearn and the reference (tests/golden/eof.json), determinism, and a full-size fit from the resident feed.
+These are tolerance tests of real-valued data; every kernel, channel count, component width, slice length and layout is pinned bit
+for bit on integer data by tests/test_eof_exact_gpu.py (case table and float64 references: tests/eof_ref.py)."""
 import json
 import os
 import types
