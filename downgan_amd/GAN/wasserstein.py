@@ -152,7 +152,7 @@ class WassersteinGAN:
 
     def gen_batch_and_log_metrics(self, coarse, fine, spectra=None, distributions=None, maps=None, fss=None, joint=None,
                                   coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None,
-                                  distances=None):
+                                  distances=None, intensity_scale=None):
         """Native version of mlflow_tools/mlflow_epoch.py:53-63 (the per-step metrics pass, wasserstein.py:140):
         returns {"MAE", "MSE", "Wass", "MSSSIM"} (MSSSIM None for tiles too small for 5 scales).  The other keywords are the
         diagnostic sinks of ``TrainEngine.metrics_pass`` (engine.METRIC_SINKS), accumulators that also receive the real and
@@ -260,6 +260,13 @@ class WassersteinGAN:
     log_distances = False
     distance_spec = None
     distance_results = None      # the last epoch's {"train" / "test": distmap.DistanceResult} when logged
+    # opt-in: intensity-scale verification of the same (real, generated) pairs -- the error of the thresholded fields split into
+    # 2-D Haar components per dyadic scale (skill, MSE and energies per threshold and scale; exact integer sums on the device,
+    # nothing per pixel), reported per epoch in summary["intensity_scale"]; intensity_scale_spec None =
+    # iscale.IscaleSpec.zscore(n_predictands)
+    log_intensity_scale = False
+    intensity_scale_spec = None
+    intensity_scale_results = None   # the last epoch's {"train" / "test": iscale.IscaleResult} when logged
     checkpoint_dir = None        # e.g. "artifacts": <dir>/Critic/Critic_<epoch>/state_dict.pth (mlflow_epoch.py:65-69 without mlflow)
 
     @staticmethod
@@ -324,6 +331,10 @@ class WassersteinGAN:
     def _distances_acc(self, fine, dev):
         from ..distmap import Distances, DistSpec
         return Distances(self._spec(self.distance_spec, DistSpec), fine.shape[-2], fine.shape[-1], device=dev)
+
+    def _iscale_acc(self, fine, dev):
+        from ..iscale import IntensityScale, IscaleSpec
+        return IntensityScale(self._spec(self.intensity_scale_spec, IscaleSpec), fine.shape[-2], fine.shape[-1], device=dev)
 
     def _hooks(self, acc, part, fine):
         """The keyword arguments of gen_batch_and_log_metrics that feed the enabled per-epoch accumulators of ``part``
@@ -505,4 +516,5 @@ HOOKS = (                                      # in the order of the epoch summa
     Hook("helmholtz", "log_helmholtz", "helmholtz", WassersteinGAN._helmholtz_acc, WassersteinGAN._helmholtz_summary),
     Hook("objects", "log_objects", "objects", WassersteinGAN._objects_acc, results="objects_results"),
     Hook("distances", "log_distances", "distances", WassersteinGAN._distances_acc, results="distance_results"),
+    Hook("intensity_scale", "log_intensity_scale", "intensity_scale", WassersteinGAN._iscale_acc, results="intensity_scale_results"),
 )

@@ -1,9 +1,9 @@
-// The field reader of the diagnostics: a series of fields in through dg_eof_fields, output values y out.  Nine translation units
+// The field reader of the diagnostics: a series of fields in through dg_eof_fields, output values y out.  Ten translation units
 // read fields this way -- the value histograms (histogram.hip), the joint histograms (joint.hip), the per-gridpoint statistics
 // (gridstats.hip) and histograms (gridhist.hip), the fractions skill score (fss.hip), the exceedance objects (objects.hip), the
-// distance maps (distmap.hip), the increment histograms (increments.hip) and the temporal diagnostics (temporal.hip) -- and all
-// must see the same output values y bit for bit, on the device and in their host references.  So y is defined here and only
-// here: the arithmetic rules (hist_affine, hist_speed, hist_diff, hist_bin, hist_dir), the load modes and how a pixel is unpacked
+// distance maps (distmap.hip), the increment histograms (increments.hip), the temporal diagnostics (temporal.hip) and the
+// intensity-scale verification (iscale.hip) -- and all must see the same output values y bit for bit, on the device and in their
+// host references.  So y is defined here and only here: the arithmetic rules (hist_affine, hist_speed, hist_diff, hist_bin, hist_dir), the load modes and how a pixel is unpacked
 // in each, the kernel-argument form of a spec's transform (HistXform) with its padding, the device loaders per access pattern
 // (hist_pixel_values, hist_load_item, hist_unit_load / hist_unit_value, hist_pick16_sel), the spec checks and the host value
 // (hist_host_value).  DESIGN.md "Field reader" says which loader serves which access pattern.
@@ -213,16 +213,31 @@ __device__ __forceinline__ float hist_pick16_shift(const uint4& r, int c) {
   return __uint_as_float((unsigned)(q >> (32 * (c & 1))));
 }
 
-// One pixel, every output channel (fss.hip, objects.hip, distmap.hip): the nout output values of the pixel whose channel 0 is at q;
-// MODE is HIST_PIX16 or HIST_ANY.  y beyond nout is 0.
+// One pixel, every output channel (fss.hip, objects.hip, distmap.hip, iscale.hip): the nout output values of the pixel whose
+// channel 0 is at q; MODE is HIST_PIX16 or HIST_ANY.  y beyond nout is 0.  hist_pixel_values is hist_pixel_load, the loads alone,
+// followed by hist_pixel_finish, everything after them: a kernel whose walk is a chain of load latencies (iscale.hip) issues the
+// loads of several pixels before it finishes the first.
+template <int MODE> struct HistPixelRaw { float v[HIST_MAXC]; };
+template <> struct HistPixelRaw<HIST_PIX16> { uint4 r; };
+
 template <typename T, int MODE>
-__device__ __forceinline__ void hist_pixel_values(const HistXform& xf, const T* q, long long ld_c, float (&y)[HIST_MAXO]) {
-  float v[HIST_MAXC];
-  if (MODE == HIST_PIX16) {
-    hist_unpack16<T>(*reinterpret_cast<const uint4*>(q), v);
+__device__ __forceinline__ void hist_pixel_load(const HistXform& xf, const T* q, long long ld_c, HistPixelRaw<MODE>& raw) {
+  if constexpr (MODE == HIST_PIX16) {
+    raw.r = *reinterpret_cast<const uint4*>(q);
   } else {
 #pragma unroll
-    for (int c = 0; c < HIST_MAXC; ++c) v[c] = c < xf.C ? ld_elem(q + c * ld_c) : 0.f;
+    for (int c = 0; c < HIST_MAXC; ++c) raw.v[c] = c < xf.C ? ld_elem(q + c * ld_c) : 0.f;
+  }
+}
+
+template <typename T, int MODE>
+__device__ __forceinline__ void hist_pixel_finish(const HistXform& xf, const HistPixelRaw<MODE>& raw, float (&y)[HIST_MAXO]) {
+  float v[HIST_MAXC];
+  if constexpr (MODE == HIST_PIX16) {
+    hist_unpack16<T>(raw.r, v);
+  } else {
+#pragma unroll
+    for (int c = 0; c < HIST_MAXC; ++c) v[c] = raw.v[c];
   }
   float yu = 0.f, yv = 0.f;
 #pragma unroll
@@ -237,6 +252,13 @@ __device__ __forceinline__ void hist_pixel_values(const HistXform& xf, const T* 
 #pragma unroll
     for (int j = 0; j < HIST_MAXO; ++j) y[j] = j == xf.C ? s : y[j];
   }
+}
+
+template <typename T, int MODE>
+__device__ __forceinline__ void hist_pixel_values(const HistXform& xf, const T* q, long long ld_c, float (&y)[HIST_MAXO]) {
+  HistPixelRaw<MODE> raw;
+  hist_pixel_load<T, MODE>(xf, q, ld_c, raw);
+  hist_pixel_finish<T, MODE>(xf, raw, y);
 }
 
 // One item, every input channel, untransformed (histogram.hip, joint.hip): item i of field t is the pixel quad i in HIST_NCHW4

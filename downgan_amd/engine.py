@@ -1011,7 +1011,7 @@ class NativeGenerator:
 # of single-series accumulators, each fed its own side, and not one accumulator fed the pair)
 METRIC_SINKS = (("spectra", True), ("coherence", False), ("helmholtz", False), ("distributions", True), ("maps", False),
                 ("fss", False), ("joint", False), ("increments", False), ("hist_maps", False), ("temporal", False),
-                ("objects", False), ("distances", False))
+                ("objects", False), ("distances", False), ("intensity_scale", False))
 
 
 class TrainEngine:
@@ -1244,7 +1244,8 @@ class TrainEngine:
                     addend=self.gbuf)                             # :78 + losses.py:51-53
 
     def metrics_pass(self, coarse, fine, n_valid=None, spectra=None, distributions=None, maps=None, fss=None, joint=None,
-                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None, distances=None):
+                     coherence=None, increments=None, hist_maps=None, temporal=None, helmholtz=None, objects=None, distances=None,
+                     intensity_scale=None):
         """Per-batch evaluation metrics of the reference's training loop (mlflow_tools/mlflow_epoch.py:53-63 called at
         wasserstein.py:140): MAE = L1(real, G(x)) (losses.py:40-55), MSE (losses.py:58-70), Wass = mean C(real) -
         mean C(G(x)) (losses.py:8-9), MSSSIM = MS-SSIM of the batch-min-max-normalised fields (losses.py:12-38; msssim.py).
@@ -1260,7 +1261,7 @@ class TrainEngine:
         (``spectra.CrossSpectrum``), ``helmholtz`` (``spectra.HelmholtzSpectrum``), ``maps`` (paired ``gridstats.GridStats``),
         ``fss`` (``fss.FractionsSkill``), ``joint`` (``joint.ValueJoint``), ``increments`` (``increments.Increments``),
         ``hist_maps`` (paired ``gridhist.GridHist``), ``temporal`` (paired ``temporal.Temporal``), ``objects`` (paired
-        ``objects.Objects``), ``distances`` (``distmap.Distances``).
+        ``objects.Objects``), ``distances`` (``distmap.Distances``), ``intensity_scale`` (``iscale.IntensityScale``).
         The histograms read the fields as stored: in bf16 mode the staged real fields and the generated ones are bf16
         (spacing 0.031 on [4, 8), coarser than the default bin width of 0.0098), so the histograms are those of the bf16
         values.  ``temporal`` takes the pair as the next n times of its series: the caller feeds the batches in time order.

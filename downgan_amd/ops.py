@@ -1108,6 +1108,30 @@ class HipOps:
         check(self.lib.dg_fss(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(sums), _ptr(rates),
                               _ptr(per_field), self._stream()), "dg_fss")
 
+    # ------------------------------------------------------------------ intensity-scale verification (csrc/iscale.hip)
+    def iscale_ws_bytes(self, f, H, W, spec):
+        """Workspace bytes of one dg_iscale call over the descriptor ``f`` (either series) of H x W fields with the
+        _lib.IscaleSpec ``spec`` (0: invalid, or more fields than one call may take: T * dg_iscale_bound > 2^62)."""
+        return int(self.lib.dg_iscale_ws_bytes(C.byref(f), int(H), int(W), C.byref(spec)))
+
+    def iscale(self, fa, fb, H, W, spec, sums, per_field=None):
+        """Accumulate the intensity-scale integers of the pair of series ``fa`` (real), ``fb`` (generated) (eof_fields, H x W
+        fields) under ``spec`` (_lib.IscaleSpec): sums int64 [nout, nthr, n + 1, 3] (D A B per level 0 .. n, 2^n >= max(H, W))
+        +=, per_field int64 [T, nout, nthr, n + 1, 3] overwritten when given.  The workspace is cached on this object."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        n = nout * spec.nthr * int(self.lib.dg_iscale_levels(int(H), int(W))) * 3
+        for out, m in ((sums, n), (per_field, fa.T * n)):
+            assert out is None or (out.dtype == torch.int64 and out.is_contiguous() and out.numel() == m and out.is_cuda), (m,)
+        assert (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.iscale_ws_bytes(fa, H, W, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, H, W, spec.nthr)
+        ws = getattr(self, "_iscale_ws", None)
+        if ws is None or ws.numel() < nb:
+            self._iscale_ws = ws = None
+            self._iscale_ws = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        check(self.lib.dg_iscale(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(sums), _ptr(per_field),
+                                 self._stream()), "dg_iscale")
+
     # ------------------------------------------------------------------ exceedance objects (csrc/objects.hip)
     def objects_ws_bytes(self, f, H, W, spec):
         """Workspace bytes of one dg_objects call over the descriptor ``f`` (either series) of H x W fields with the

@@ -731,6 +731,51 @@ int dg_fss(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const d
 int dg_fss_host(const dg_fss_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* sums, int64_t* rates);
 int64_t dg_fss_bound(int H, int W, int win);
 
+/* ---- Intensity-scale verification (csrc/iscale.hip) --------------------------------------------------------------------------
+ * At which spatial scale, for which intensity, does the error of the generated field live (Casati, Ross & Stephenson 2004; the
+ * energies of Casati 2010): the error of the thresholded fields split into orthogonal 2-D Haar components, one per dyadic scale,
+ * so that the mean squared error adds up over the scales.  Fields, series, output values y and masks are those of the fractions
+ * skill score above (the same code, csrc/hist_common.h): I_a[t,p] = (y_a > thr[j][k]), an fp32 compare (NaN false, +inf true,
+ * equality false), I_b likewise.  Let n be the smallest integer with 2^n >= max(H, W); the masks are zero outside the grid, on
+ * the 2^n x 2^n square anchored at pixel (0, 0).  For level l = 0 .. n the square is tiled into aligned blocks of side 2^l, and
+ * with S_l(X, block) the sum of X over a block, per output channel j, threshold k and level l:
+ *   sums           D_l = sum (S_l(I_b) - S_l(I_a))^2,  A_l = sum S_l(I_a)^2,  B_l = sum S_l(I_b)^2   over all t and blocks, exact
+ *                  integers; D_0 = the disagreeing pixels, A_0 = N_a, B_0 = N_b (dg_fss's D, A, B at window 1)
+ *   components     formed on the host from the integers, E = D, A or B: the Haar (mother) component of the features of side
+ *                  2^(l-1) is E_(l-1) / 4^(l-1) - E_l / 4^l, l = 1 .. n, the father component E_n / 4^n; they sum to E_0
+ * One kernel reads every pixel of both series once: a workgroup of four waves owns a 64 x 64 tile, takes the masks of all (j, k) of a row as wave
+ * ballots (one 64-bit word per row and side, kept in LDS), counts the levels 0 .. 6 with popcounts, packed adds and xor shuffles
+ * and adds them with 64-bit integer atomics into per-field slots of the workspace; the tile totals (two counts <= 4096) go to
+ * the workspace, and for n > 6 a second kernel builds the levels 7 .. n over the <= 32 x 32 tiles in LDS, one workgroup per
+ * (t, j, k); the last adds the slots to the accumulators.  No per-pixel workspace, no float after the compare and only integer
+ * atomics: the results are exact and two calls on the same data are bit-identical.
+ *
+ * dg_iscale_levels: host-side, n + 1 (the number of levels 0 .. n); 0 when H or W is outside 1 .. DG_ISCALE_MAX_SIDE.
+ * dg_iscale_bound: host-side, 16^n, the most one field adds to any entry (2^44 at 2048 x 2048); 0 when H or W is invalid.
+ * dg_iscale_ws_bytes: workspace bytes of one call (0 for an invalid descriptor, grid or spec): the per-field slots and one
+ *   4-byte total per (t, j, k, tile).
+ * dg_iscale: sums int64 [nout][nthr][n+1][3] (D A B) ACCUMULATE (the caller zeroes them and owns their headroom); per_field
+ *   int64 [T][nout][nthr][n+1][3] is overwritten and may be NULL.  Rejected before any launch: descriptors that differ in
+ *   T / C / P, P != H*W, H or W above DG_ISCALE_MAX_SIDE, a non-finite thr / scale / offset, and T * dg_iscale_bound > 2^62 (one
+ *   call cannot overflow).
+ * dg_iscale_host: host-side, the same definition by loops over the blocks for one field pair, planar fp32 [C][H][W]; sums
+ *   [nout][nthr][n+1][3] +=. */
+#define DG_ISCALE_MAX_THR 4
+#define DG_ISCALE_MAX_LEVELS 12         /* n + 1 at DG_ISCALE_MAX_SIDE */
+#define DG_ISCALE_MAX_SIDE 2048         /* H, W */
+typedef struct dg_iscale_spec {
+  int speed_u, speed_v;                 /* input channels of the speed channel, or -1, -1: none */
+  int nthr;                             /* 1 .. DG_ISCALE_MAX_THR */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float thr[DG_HIST_MAX_OUT][DG_ISCALE_MAX_THR];     /* per output channel, the first nthr finite */
+} dg_iscale_spec;
+int dg_iscale_levels(int H, int W);
+int64_t dg_iscale_bound(int H, int W);
+size_t dg_iscale_ws_bytes(const dg_eof_fields* a, int H, int W, const dg_iscale_spec* s);
+int dg_iscale(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_iscale_spec* s, void* ws, int64_t* sums,
+              int64_t* per_field, void* stream);
+int dg_iscale_host(const dg_iscale_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* sums);
+
 /* ---- Joint histograms (csrc/joint.hip) -------------------------------------------------------------------------------------
  * Wind roses and real-vs-generated densities: 2-D histograms over one or two series of fields of equal T, C, P, each read in
  * place through the EOF descriptor (NCHW fp32 / bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC
