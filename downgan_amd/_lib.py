@@ -82,6 +82,7 @@ HIST_MAX_BINS, HIST_MAX_OUT = 4096, EOF_MAX_C + 1
 GRID_MAX_THR = 4
 FSS_MAX_THR, FSS_MAX_SCALES, FSS_MAX_SIDE = 4, 8, 2048
 ISCALE_MAX_THR, ISCALE_MAX_LEVELS, ISCALE_MAX_SIDE = 4, 12, 2048
+DEFORM_MAX_LEVELS, DEFORM_MAX_SIDE, DEFORM_SCALARS = 4, 2048, 5
 HIST2D_MAX_PAIRS, HIST2D_MAX_CELLS, HIST2D_MAX_SECTORS = 8, 16384, 72
 INCR_MAX_LAGS, INCR_MAX_LAG, INCR_MAX_BINS, INCR_MAX_SIDE = 8, 256, 512, 2048
 GRIDHIST_MAX_BINS, GRIDHIST_MAX_Q = 256, 16
@@ -115,6 +116,11 @@ class FssSpec(C.Structure):
 class IscaleSpec(C.Structure):
     _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("nthr", C.c_int), ("scale", C.c_float * EOF_MAX_C),
                 ("offset", C.c_float * EOF_MAX_C), ("thr", (C.c_float * ISCALE_MAX_THR) * HIST_MAX_OUT)]
+
+
+class DeformSpec(C.Structure):
+    _fields_ = [("speed_u", C.c_int), ("speed_v", C.c_int), ("levels", C.c_int), ("scale", C.c_float * EOF_MAX_C),
+                ("offset", C.c_float * EOF_MAX_C), ("lo", C.c_float * HIST_MAX_OUT), ("inv_step", C.c_float * HIST_MAX_OUT)]
 
 
 class Hist2dAxis(C.Structure):
@@ -247,6 +253,12 @@ _PROTOS = {
     "dg_iscale_ws_bytes": [C.POINTER(EofFields), _i, _i, C.POINTER(IscaleSpec)],
     "dg_iscale": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(IscaleSpec), _vp, _vp, _vp, _vp],
     "dg_iscale_host": [C.POINTER(IscaleSpec), _vp, _vp, _i, _i, _i, _vp],
+    "dg_deform_bound": [_i, _i],
+    "dg_deform_ws_bytes": [C.POINTER(EofFields), _i, _i, C.POINTER(DeformSpec)],
+    "dg_deform": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(DeformSpec), _vp, _vp, _vp, _vp],
+    "dg_deform_field": [C.POINTER(EofFields), C.POINTER(EofFields), _i, _i, C.POINTER(DeformSpec), _vp, _vp, _vp, _vp],
+    "dg_deform_host": [C.POINTER(DeformSpec), _vp, _vp, _i, _i, _i, _vp, _vp],
+    "dg_deform_field_host": [C.POINTER(DeformSpec), _vp, _vp, _i, _i, _i, _vp, _vp],
     "dg_hist2d_ws_bytes": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(Hist2dSpec)],
     "dg_hist2d": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(Hist2dSpec), _vp, _vp, _vp],
     "dg_hist2d_host_bins": [C.POINTER(Hist2dSpec), _vp, _vp, _i, _i64, _vp],
@@ -275,7 +287,8 @@ _RESTYPES = {"dg_rapsd_ws_bytes": C.c_size_t, "dg_cross_rapsd_ws_bytes": C.c_siz
              "dg_fss_ws_bytes": C.c_size_t, "dg_fss_bound": C.c_int64, "dg_hist2d_ws_bytes": C.c_size_t,
              "dg_incr_ws_bytes": C.c_size_t, "dg_gridhist_ws_bytes": C.c_size_t,
              "dg_temporal_ws_bytes": C.c_size_t, "dg_objects_ws_bytes": C.c_size_t,
-             "dg_distmap_ws_bytes": C.c_size_t, "dg_iscale_ws_bytes": C.c_size_t, "dg_iscale_bound": C.c_int64}      # every other entry point returns a dg_status
+             "dg_distmap_ws_bytes": C.c_size_t, "dg_iscale_ws_bytes": C.c_size_t, "dg_iscale_bound": C.c_int64,
+             "dg_deform_ws_bytes": C.c_size_t, "dg_deform_bound": C.c_int64}      # every other entry point returns a dg_status
 EXPORTS = ["dg_version"] + list(_PROTOS)
 
 _lib = None

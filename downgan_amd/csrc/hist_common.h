@@ -1,8 +1,8 @@
-// The field reader of the diagnostics: a series of fields in through dg_eof_fields, output values y out.  Ten translation units
+// The field reader of the diagnostics: a series of fields in through dg_eof_fields, output values y out.  Eleven translation units
 // read fields this way -- the value histograms (histogram.hip), the joint histograms (joint.hip), the per-gridpoint statistics
 // (gridstats.hip) and histograms (gridhist.hip), the fractions skill score (fss.hip), the exceedance objects (objects.hip), the
-// distance maps (distmap.hip), the increment histograms (increments.hip), the temporal diagnostics (temporal.hip) and the
-// intensity-scale verification (iscale.hip) -- and all must see the same output values y bit for bit, on the device and in their
+// distance maps (distmap.hip), the increment histograms (increments.hip), the temporal diagnostics (temporal.hip), the
+// intensity-scale verification (iscale.hip) and the field-deformation verification (deform.hip) -- and all must see the same output values y bit for bit, on the device and in their
 // host references.  So y is defined here and only here: the arithmetic rules (hist_affine, hist_speed, hist_diff, hist_bin, hist_dir), the load modes and how a pixel is unpacked
 // in each, the kernel-argument form of a spec's transform (HistXform) with its padding, the device loaders per access pattern
 // (hist_pixel_values, hist_load_item, hist_unit_load / hist_unit_value, hist_pick16_sel), the spec checks and the host value
@@ -213,7 +213,7 @@ __device__ __forceinline__ float hist_pick16_shift(const uint4& r, int c) {
   return __uint_as_float((unsigned)(q >> (32 * (c & 1))));
 }
 
-// One pixel, every output channel (fss.hip, objects.hip, distmap.hip, iscale.hip): the nout output values of the pixel whose
+// One pixel, every output channel (fss.hip, objects.hip, distmap.hip, iscale.hip, deform.hip): the nout output values of the pixel whose
 // channel 0 is at q; MODE is HIST_PIX16 or HIST_ANY.  y beyond nout is 0.  hist_pixel_values is hist_pixel_load, the loads alone,
 // followed by hist_pixel_finish, everything after them: a kernel whose walk is a chain of load latencies (iscale.hip) issues the
 // loads of several pixels before it finishes the first.

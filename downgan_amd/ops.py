@@ -1132,6 +1132,47 @@ class HipOps:
         check(self.lib.dg_iscale(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(sums), _ptr(per_field),
                                  self._stream()), "dg_iscale")
 
+    # ------------------------------------------------------------------ field-deformation verification (csrc/deform.hip)
+    def deform_ws_bytes(self, f, H, W, spec):
+        """Workspace bytes of one dg_deform / dg_deform_field call over the descriptor ``f`` (either series) of H x W fields with
+        the _lib.DeformSpec ``spec`` (0: invalid, or more fields than one call may take: T H W > 2^31)."""
+        return int(self.lib.dg_deform_ws_bytes(C.byref(f), int(H), int(W), C.byref(spec)))
+
+    def _deform_ws(self, fa, fb, H, W, spec):
+        assert (fb.T, fb.C, fb.P) == (fa.T, fa.C, fa.P), ((fa.T, fa.C, fa.P), (fb.T, fb.C, fb.P))
+        nb = self.deform_ws_bytes(fa, H, W, spec)
+        assert nb > 0, (fa.T, fa.C, fa.P, H, W, spec.levels)
+        ws = getattr(self, "_deform_ws_buf", None)
+        if ws is None or ws.numel() < nb:
+            self._deform_ws_buf = ws = None
+            self._deform_ws_buf = ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        return ws
+
+    def deform(self, fa, fb, H, W, spec, disp, scalars):
+        """Accumulate the field-deformation integers of the pair of series ``fa`` (real), ``fb`` (generated) (eof_fields, H x W
+        fields) under ``spec`` (_lib.DeformSpec): disp int64 [nout, 2, (2 D + 1)^2] (the displacement vectors over the target's
+        non-empty pixels, D = 2 (2^(levels + 1) - 1)) +=, scalars int64 [nout, 2, 5] (n_target, n_either, sse_morphed, sse_raw,
+        energy) +=; direction 0: target real, 1: target generated.  The workspace is cached on this object."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        side = 2 * (2 * ((2 << spec.levels) - 1)) + 1
+        for out, m in ((disp, nout * 2 * side * side), (scalars, nout * 2 * _lib.DEFORM_SCALARS)):
+            assert out.dtype == torch.int64 and out.is_contiguous() and out.numel() == m and out.is_cuda, (m,)
+        ws = self._deform_ws(fa, fb, H, W, spec)
+        check(self.lib.dg_deform(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(disp), _ptr(scalars),
+                                 self._stream()), "dg_deform")
+
+    def deform_field(self, fa, fb, H, W, spec, field, morphed=None):
+        """The displacement fields of the pair of series ``fa``, ``fb`` under ``spec``: field int16 [T, nout, 2, 2, H, W]
+        (direction, then (dy, dx)) and, when given, morphed uint8 [T, nout, 2, H, W] (the quantised source moved onto the
+        target) are overwritten."""
+        nout = fa.C + (1 if spec.speed_u >= 0 else 0)
+        n = fa.T * nout * 2 * int(H) * int(W)
+        assert field.dtype == torch.int16 and field.is_contiguous() and field.numel() == 2 * n and field.is_cuda, (n,)
+        assert morphed is None or (morphed.dtype == torch.uint8 and morphed.is_contiguous() and morphed.numel() == n and morphed.is_cuda)
+        ws = self._deform_ws(fa, fb, H, W, spec)
+        check(self.lib.dg_deform_field(C.byref(fa), C.byref(fb), int(H), int(W), C.byref(spec), _ptr(ws), _ptr(field), _ptr(morphed),
+                                       self._stream()), "dg_deform_field")
+
     # ------------------------------------------------------------------ exceedance objects (csrc/objects.hip)
     def objects_ws_bytes(self, f, H, W, spec):
         """Workspace bytes of one dg_objects call over the descriptor ``f`` (either series) of H x W fields with the

@@ -776,6 +776,69 @@ int dg_iscale(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, cons
               int64_t* per_field, void* stream);
 int dg_iscale_host(const dg_iscale_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* sums);
 
+/* ---- Field-deformation verification (csrc/deform.hip) ------------------------------------------------------------------------
+ * By which vector, at which place, does the generated field have to be moved to lie on the real one, and how much error is left
+ * once it has been moved: the pyramidal image matcher and the displacement / amplitude split of Keil & Craig (2007, 2009).
+ * Fields, series and output values y are those of the fractions skill score above (the same code, csrc/hist_common.h).
+ *   quantiser      b = hist_bin(y, lo[j], inv_step[j], 254) in fp32 (the bin rule of the value histograms); q = 0 for the
+ *                  underflow code 0 and the NaN code 256, q = b for 1 .. 254, q = 255 for the overflow code 255.  q in 0 .. 255;
+ *                  lo is the threshold below which the field counts as empty.  Everything after this is integer.
+ *   pyramid        F = levels, 1 .. DG_DEFORM_MAX_LEVELS.  P_0 = q; P_l[i,j] = the SUM of the 2 x 2 block of P_(l-1), zeros
+ *                  beyond the grid; level l is ceil(H / 2^l) x ceil(W / 2^l), P_l <= 255 * 4^l <= 65280 (uint16).
+ *   matching       "target X, source Y", run in both directions: direction 0 has X = a (real), Y = b (generated), direction 1
+ *                  the other way round.  For l = F down to 0, at every level-l pixel p:
+ *                    init[p]  = 2 * d_(l+1)[p >> 1]           (0 for l = F; init and Y_l read as 0 outside the level's grid)
+ *                    Y'[x]    = Y_l[x + init[x]]              (0 outside the grid)
+ *                    cost(p, s) = sum over w in [-2,2]^2 of (X_l[p+w] - Y'[p+w+s])^2,  s = (sy, sx) in [-2,2]^2
+ *                    s*       = the s of least cost; of equal costs the first in the order sorted by (sy^2 + sx^2, sy, sx):
+ *                               the zero shift wins every tie
+ *                    d_l[p]   = s* + init[p + s*]             the composition of backward warps: Y_0[p + d_0[p]] is the morphed
+ *                                                             field M (0 where p + d_0[p] is outside the grid)
+ *                  |d_0| components <= D = 2 (2^(F+1) - 1) (30 at F = 3, 62 at F = 4).  A cost is <= 25 (255 * 4^l)^2: below
+ *                  2^32 for l <= 2, 64 bits for l = 3, 4.
+ *   sums           exact integers per (output channel, direction) over all fields:
+ *                    disp[(2D+1)^2]   counts of the vector d_0[p] over the pixels with X_0[p] > 0, index (dy+D)(2D+1) + dx+D
+ *                    scalars[5]       n_target = #{X_0 > 0}, n_either = #{X_0 > 0 or M > 0}, sse_morphed = sum (X_0 - M)^2,
+ *                                     sse_raw = sum (X_0 - Y_0)^2, energy = sum X_0^2
+ * A kernel per series quantises every pixel once (uint8), one per level halves the pyramid (uint16), one per level matches both
+ * directions of every field: a workgroup owns a 64 x 32 tile, stages X_l (halo 2), Y' (halo 4, one gather through the parent
+ * displacement each) and init (halo 2) in LDS; a thread owns one column of 8 pixels and for each of the 25 shifts, in the tie
+ * order, sums the squared differences of a row of 5 once per row and slides the 5 rows down its column, keeping the best cost
+ * with a strict <.  The last kernel forms M and the sums: the displacement table as an LDS histogram per workgroup, flushed by one
+ * 64-bit integer atomic per non-zero bin.  No float after the quantiser, integer atomics only: exact, and two calls on the same
+ * data are bit-identical.
+ *
+ * dg_deform_bound: host-side, 65025 H W, the most one field adds to any sum; 0 when H or W is outside 1 .. DG_DEFORM_MAX_SIDE.
+ * dg_deform_ws_bytes: workspace bytes of one call (0 for an invalid descriptor, grid or spec, for T * H * W > 2^31 and for
+ *   T * dg_deform_bound > 2^62): per field, output channel and side the pyramid, per direction the displacements of all levels.
+ * dg_deform: disp int64 [nout][2][(2D+1)^2] and scalars int64 [nout][2][5] ACCUMULATE (the caller zeroes them and owns their
+ *   headroom).  Rejected before any launch: descriptors that differ in T / C / P, P != H*W, levels outside 1 ..
+ *   DG_DEFORM_MAX_LEVELS, a non-finite lo / scale / offset, an inv_step that is not finite and > 0, and what dg_deform_ws_bytes
+ *   rejects.
+ * dg_deform_field: d_0 as int16 [T][nout][2 directions][2 (dy, dx)][H][W] and, unless NULL, M as uint8 [T][nout][2][H][W];
+ *   both overwritten.  The same checks and workspace as dg_deform.
+ * dg_deform_host / dg_deform_field_host: host-side, the same definition for one field pair, planar fp32 [C][H][W], by the plain
+ *   625-term loop per pixel; disp and scalars +=, field int16 [nout][2][2][H][W] and morphed uint8 [nout][2][H][W] (or NULL)
+ *   overwritten. */
+#define DG_DEFORM_MAX_LEVELS 4
+#define DG_DEFORM_MAX_SIDE 2048         /* H, W */
+#define DG_DEFORM_SCALARS 5
+typedef struct dg_deform_spec {
+  int speed_u, speed_v;                 /* input channels of the speed channel, or -1, -1: none */
+  int levels;                           /* F: 1 .. DG_DEFORM_MAX_LEVELS */
+  float scale[DG_EOF_MAX_C], offset[DG_EOF_MAX_C];   /* per input channel, finite */
+  float lo[DG_HIST_MAX_OUT], inv_step[DG_HIST_MAX_OUT];   /* per output channel: finite; finite and > 0 */
+} dg_deform_spec;
+int64_t dg_deform_bound(int H, int W);
+size_t dg_deform_ws_bytes(const dg_eof_fields* a, int H, int W, const dg_deform_spec* s);
+int dg_deform(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_deform_spec* s, void* ws, int64_t* disp,
+              int64_t* scalars, void* stream);
+int dg_deform_field(const dg_eof_fields* a, const dg_eof_fields* b, int H, int W, const dg_deform_spec* s, void* ws,
+                    int16_t* field, uint8_t* morphed, void* stream);
+int dg_deform_host(const dg_deform_spec* s, const float* a, const float* b, int C, int H, int W, int64_t* disp, int64_t* scalars);
+int dg_deform_field_host(const dg_deform_spec* s, const float* a, const float* b, int C, int H, int W, int16_t* field,
+                         uint8_t* morphed);
+
 /* ---- Joint histograms (csrc/joint.hip) -------------------------------------------------------------------------------------
  * Wind roses and real-vs-generated densities: 2-D histograms over one or two series of fields of equal T, C, P, each read in
  * place through the EOF descriptor (NCHW fp32 / bf16, the resident feed's [n, H, W, c] store, the generator's padded NHWC
