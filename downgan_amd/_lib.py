@@ -270,6 +270,10 @@ _PROTOS = {
     "dg_gridhist_scan": [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp, _vp],
     "dg_gridhist_host": [C.POINTER(HistSpec), _vp, _vp, _i, _i, _i, _vp],
     "dg_gridhist_scan_host": [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), _i, _vp, _vp],
+    "dg_qmap_fit": [_vp, _i, _i, _i, C.POINTER(_f), C.POINTER(C.c_double), _vp, _vp],
+    "dg_qmap_apply": [C.POINTER(EofFields), C.POINTER(HistSpec), _vp, _vp, _vp],
+    "dg_qmap_fit_host": [_vp, _i, _i, _i, C.POINTER(_f), C.POINTER(C.c_double), _vp],
+    "dg_qmap_apply_host": [C.POINTER(HistSpec), _vp, _i, _i, _i, _vp, _vp],
     "dg_temporal_ws_bytes": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(TemporalSpec)],
     "dg_temporal": [C.POINTER(EofFields), C.POINTER(EofFields), C.POINTER(TemporalSpec), _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                     _vp],

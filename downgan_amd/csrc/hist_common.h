@@ -1,7 +1,8 @@
-// The field reader of the diagnostics: a series of fields in through dg_eof_fields, output values y out.  Eleven translation units
+// The field reader of the diagnostics: a series of fields in through dg_eof_fields, output values y out.  Twelve translation units
 // read fields this way -- the value histograms (histogram.hip), the joint histograms (joint.hip), the per-gridpoint statistics
-// (gridstats.hip) and histograms (gridhist.hip), the fractions skill score (fss.hip), the exceedance objects (objects.hip), the
-// distance maps (distmap.hip), the increment histograms (increments.hip), the temporal diagnostics (temporal.hip), the
+// (gridstats.hip) and histograms (gridhist.hip), the quantile mapping fitted on them (qmap.hip), the fractions skill score
+// (fss.hip), the exceedance objects (objects.hip), the distance maps (distmap.hip), the increment histograms (increments.hip),
+// the temporal diagnostics (temporal.hip), the
 // intensity-scale verification (iscale.hip) and the field-deformation verification (deform.hip) -- and all must see the same output values y bit for bit, on the device and in their
 // host references.  So y is defined here and only here: the arithmetic rules (hist_affine, hist_speed, hist_diff, hist_bin, hist_dir), the load modes and how a pixel is unpacked
 // in each, the kernel-argument form of a spec's transform (HistXform) with its padding, the device loaders per access pattern

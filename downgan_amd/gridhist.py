@@ -16,7 +16,7 @@ into calls, on layout or on dtype (bf16 inputs are the values the kernel reads);
 (integer atomics only).  ``GridHist`` accumulates batches on the device (and over data-parallel ranks), the trainer's opt-in hook
 (``WassersteinGAN.log_quantile_maps``) keeps one per part, and ``GridHistMaps`` derives the maps: a second kernel scans the table
 on the device into integer quantile ranks and the integer W1 / KS sums, and only those maps come to the host, where float64
-finishes them.  The tables are also the input of empirical quantile mapping (not applied here).
+finishes them.  The tables are also the input of empirical quantile mapping (``downgan_amd.qmap``: ``QuantileMap.fit`` of a paired result).
 """
 from __future__ import annotations
 

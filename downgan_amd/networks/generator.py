@@ -71,9 +71,20 @@ class Generator(NativeModule):
 
     __call__ = forward
 
-    def generate(self, coarse, chunk_size=None):
+    def generate(self, coarse, chunk_size=None, qmap=None):
         """Chunked inference over a long series of coarse fields, like the reference's generation script
-        (reference DoWnGAN/helpers/gen_fake_ds.py:147-162: ``G(chunk)`` per chunk, concatenated on the host)."""
+        (reference DoWnGAN/helpers/gen_fake_ds.py:147-162: ``G(chunk)`` per chunk, concatenated on the host).  ``qmap``: a
+        ``qmap.QuantileMap`` fitted on a calibration part (its spec: one input channel per predictand, no speed channel); each
+        chunk's output is then bias-corrected on the device before it goes to the host."""
+        if qmap is not None:
+            from ..qmap import QuantileMap
+            if not isinstance(qmap, QuantileMap):
+                raise TypeError(f"generate takes a qmap.QuantileMap (got {type(qmap).__name__})")
+            if qmap.spec.C != self.n_predictands or qmap.spec.speed is not None:
+                raise ValueError(f"generate maps the {self.n_predictands} predictands channel by channel: the QuantileMap's spec must "
+                                 f"describe C = {self.n_predictands} input channels and no speed channel (got C = {qmap.spec.C}, "
+                                 f"speed = {qmap.spec.speed})")
+        fix = (lambda y: y) if qmap is None else qmap.apply
         n = coarse.shape[0]
         chunk_size = chunk_size or n
         outs = []
@@ -81,7 +92,7 @@ class Generator(NativeModule):
             part = coarse[i:i + chunk_size]
             if part.shape[0] < chunk_size and i > 0:      # pad the ragged tail so one native instance serves all chunks
                 pad = torch.zeros(chunk_size - part.shape[0], *part.shape[1:], dtype=part.dtype, device=part.device)
-                outs.append(self.forward(torch.cat([part, pad], 0))[:part.shape[0]].cpu())
+                outs.append(fix(self.forward(torch.cat([part, pad], 0))[:part.shape[0]]).cpu())
             else:
-                outs.append(self.forward(part).cpu())
+                outs.append(fix(self.forward(part)).cpu())
         return torch.cat(outs, 0)

@@ -1052,6 +1052,28 @@ class HipOps:
         check(self.lib.dg_gridhist_scan(_ptr(counts), nout, S, nb3 - 3, P, qa, Q, _ptr(ranks), _ptr(dist), self._stream()),
               "dg_gridhist_scan")
 
+    # ------------------------------------------------------------------ empirical quantile mapping (csrc/qmap.hip)
+    def qmap_fit(self, counts, lo, width, nodes):
+        """Fit the per-pixel transfer functions of a paired per-pixel histogram table counts int32 [nout, 2, nbins + 3, P] (real,
+        generated) with the bin origins ``lo`` (fp32) and widths ``width`` (fp64), one per output channel: nodes fp32
+        [nout, nbins + 3, P] is overwritten (rows: include/downgan_hip.h)."""
+        nout, S, nb3, P = counts.shape
+        assert S == 2 and counts.dtype == torch.int32 and counts.is_contiguous() and counts.is_cuda, (counts.dtype, counts.shape)
+        assert nodes.dtype == torch.float32 and nodes.is_contiguous() and nodes.is_cuda and tuple(nodes.shape) == (nout, nb3, P), nodes.shape
+        assert len(lo) == nout and len(width) == nout, (len(lo), len(width), nout)
+        la = (C.c_float * nout)(*[float(v) for v in lo])
+        wa = (C.c_double * nout)(*[float(v) for v in width])
+        check(self.lib.dg_qmap_fit(_ptr(counts), nout, nb3 - 3, P, la, wa, _ptr(nodes), self._stream()), "dg_qmap_fit")
+
+    def qmap_apply(self, f, spec, nodes, out):
+        """Map the fields of ``f`` (eof_fields) under ``spec`` (_lib.HistSpec) through the transfer functions nodes fp32
+        [nout, nbins + 3, P] of ``qmap_fit``: out fp32 [T, nout, P] (any trailing shape of P elements) is overwritten."""
+        nout = f.C + (1 if spec.speed_u >= 0 else 0)
+        assert nodes.dtype == torch.float32 and nodes.is_contiguous() and nodes.is_cuda and nodes.numel() == nout * (spec.nbins + 3) * f.P, \
+            (nodes.dtype, nodes.shape)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.is_cuda and out.numel() == f.T * nout * f.P, (out.dtype, out.shape)
+        check(self.lib.dg_qmap_apply(C.byref(f), C.byref(spec), _ptr(nodes), _ptr(out), self._stream()), "dg_qmap_apply")
+
     # ------------------------------------------------------------------ temporal diagnostics (csrc/temporal.hip)
     def temporal_ws_bytes(self, fa, fb, spec):
         """Workspace bytes of one dg_temporal call over the descriptors ``fa`` (and ``fb``, or None) with the _lib.TemporalSpec

@@ -993,6 +993,49 @@ int dg_gridhist_host(const dg_hist_spec* s, const float* xa, const float* xb, in
 int dg_gridhist_scan_host(const int32_t* counts, int nout, int S, int nbins, int P, const double* q, int Q, int32_t* ranks,
                           int64_t* dist);
 
+/* ---- Empirical quantile mapping (csrc/qmap.hip) -----------------------------------------------------------------------------
+ * The per-gridpoint bias correction y' = F_real^-1(F_gen(y)) (the bias-correction half of BCSD, the "GAN + QM" baseline), fitted
+ * on a paired dg_gridhist table and applied to series of fields read through the EOF descriptor.  Every step is integer arithmetic
+ * or one correctly rounded floating-point operation with contraction off, so the device and the host references agree bit for bit.
+ *
+ * dg_qmap_fit: counts int32 [nout][2][nbins + 3][P] as dg_gridhist writes it (side 0 real = the target, side 1 generated = the
+ * source), lo[j] (fp32) and width[j] (fp64, the nominal bin width (hi - lo) / nbins; both HOST pointers, nout entries, lo finite,
+ * width > 0) -> nodes fp32 [nout][nbins + 3][P], the pixel index fastest.  Per (j, p), a[r] the generated and b[r] the real row:
+ *   n_g = sum_{r = 0 .. nbins + 1} a[r], n_r likewise;  G_k = sum_{r <= k} a[r], B_s = sum_{r <= s} b[r], k, s = 0 .. nbins: the
+ *   cumulative counts at the bin edges e_k = lo + k w (row 0 is the underflow mass).
+ *   n_g = 0 or n_r = 0: pos_k = k (nothing to calibrate on: the identity).  Otherwise in int64 X = G_k n_r, B'_s = B_s n_g (fewer than
+ *   2^26 fields: every product is below 2^52 and converts to fp64 exactly) and
+ *     X > B'_nbins:  plo = phi = nbins                                    (the target lies in the real overflow mass)
+ *     X <= B'_0:     plo = 0, phi = max{s : B'_s <= X} (0 when there is none)
+ *     otherwise:     s = the smallest index in 1 .. nbins with B'_s >= X (so b[s] > 0);
+ *                    plo = fp64(s - 1) + fp64(X - B'_{s-1}) / fp64(b[s] n_g)   (one division, one addition)
+ *                    phi = max(plo, max{s : B'_s <= X})
+ *   pos_k = min(max(fp64(k), plo), phi): where the real CDF is flat at the target its inverse is an interval, and the node takes
+ *   the point of it nearest to the edge itself -- the least correction, and a == b gives the identity exactly, empty bins included.
+ *   nodes[k]         = fp32(fp64(lo) + pos_k w), k = 0 .. nbins           (one fp64 multiply, one fp64 add, one rounding)
+ *   nodes[nbins + 1] = d_lo = nodes[0] - lo                               (fp32)
+ *   nodes[nbins + 2] = d_hi = nodes[nbins] - fp32(fp64(lo) + nbins w)     (fp32)
+ * One lane owns its pixel (four pixels, with 16-byte row accesses, where P % 4 == 0 and the arrays are 16-byte aligned): a first walk
+ * for n_g and n_r, then one merge walk in which k, s and the phi pointer only advance.  No LDS, no atomics.
+ *
+ * dg_qmap_apply: the series x (every layout and dtype dg_gridhist takes), the dg_hist_spec the table was made with (the checks of
+ * dg_gridhist) and nodes -> out fp32 [T][nout][P], planar.  Per output value y of the spec (hist_affine, hist_speed), with t and the row
+ * r exactly as hist_bin makes them:
+ *   NaN row: the quiet NaN 0x7fc00000;   r = 0: y + d_lo;   r = nbins + 1: y + d_hi   (beyond the calibrated range a constant shift)
+ *   interior, k = r - 1:  f = t - (float)k;  dm = nodes[k + 1] - nodes[k];  out = nodes[k] + f dm   (three rounded fp32 operations)
+ * A workgroup stages the transfer functions of 64 consecutive pixels of one output channel in LDS as [node][pixel] ((nbins + 3) * 256
+ * bytes; a lane's reads hit bank pixel mod 32, distinct within its group of 32 lanes) and its waves stream the fields of its slice past them; the fields are cut into
+ * slices over blockIdx.y when P alone does not fill the chip.  out is overwritten, two calls are bit-identical, and the result
+ * does not depend on how the fields were chunked into calls.
+ *
+ * dg_qmap_fit_host / dg_qmap_apply_host: host-side, the same definitions in plain C++ on host arrays; x planar fp32 [T][C][P].
+ * Status codes as dg_gridhist: DG_ERR_BAD_SHAPE for a NULL pointer, nout, nbins, P, T or a spec out of range, DG_ERR_BAD_DTYPE for
+ * a dtype other than fp32 / bf16; nothing is launched then. */
+int dg_qmap_fit(const int32_t* counts, int nout, int nbins, int P, const float* lo, const double* width, float* nodes, void* stream);
+int dg_qmap_apply(const dg_eof_fields* x, const dg_hist_spec* s, const float* nodes, float* out, void* stream);
+int dg_qmap_fit_host(const int32_t* counts, int nout, int nbins, int P, const float* lo, const double* width, float* nodes);
+int dg_qmap_apply_host(const dg_hist_spec* s, const float* x, int C, int T, int P, const float* nodes, float* out);
+
 /* ---- Temporal diagnostics (csrc/temporal.hip) -------------------------------------------------------------------------------
  * Every other diagnostic treats the fields of a series as an unordered sample; this one looks along the time axis of one series:
  * how long a gridpoint stays above / below a threshold (spell durations), how fast it changes (ramps y(t) - y(t - tau)) and how
